@@ -4,6 +4,8 @@ samples/sec for the whole node, one process per GPU over RCCL.
 
     python bench.py --gpus N --steps K --warmup W          (N=1)
     torchrun --nproc-per-node N bench.py --gpus N ...      (N>1)
+    ... --full                 also what takes runs of its own (the per-bucket communication step at N>1)
+    ... --dump-outputs DIR     the timed step's loss and (sampled) updated model as DIR/*.npy (see below)
 
 Per step (all inside the timed region): forward, fused cross-entropy,
 backward with bucketed RCCL all-reduce overlapped on a side stream, fused SGD
@@ -15,6 +17,15 @@ batch BASELINE.json names for ResNet-50 (config 5); measured on one MI355X:
 256 -> 9.2k, 512 -> 10.0k, 1024 -> 10.7k img/s; stock PyTorch-ROCm 6.3k / 6.7k
 at 256 / 512).
 Rank 0 prints ONE JSON line.
+
+--dump-outputs: the inputs and the initial weights are seeded, so two runs see identical data.  Thirteen
+ResNet-50 weight gradients (the stem, the 1x1 convs of layers 1-2 and layer 2's 3x3) are summed with float
+atomics, which leaves last-bit run-to-run noise, and training at lr 0.1 from random init amplifies it step
+by step: the trained parameters of two runs of ONE build agree to 4e-9 (relative L2) after 1 step, 1.4e-2
+after 3 and 0.18 after 25 -- no basis for comparing two builds.  So what is dumped is the timed path run
+once more after the timed steps, untimed: the same step function on the last timed step's batch, from the
+seeded state (weights and buffers restored in place, optimizer state zeroed).  Its loss and updated model
+repeat from run to run to that last-bit noise, for any --steps / --warmup.
 """
 from __future__ import annotations
 
@@ -59,7 +70,7 @@ def parse():
     ap.add_argument("--bucket-timing", type=int, default=None,
                     help="1: after the timed steps, one instrumented (untimed) step: per-bucket all-reduce time and "
                          "its overlap with backward (HIP events on the RCCL stream), reported under 'buckets' "
-                         "(default: on at world size > 1, so a multi-GPU run documents its communication)")
+                         "(default: on with --full at world size > 1, so such a run documents its communication)")
     ap.add_argument("--force-comm", action="store_true",
                     help="run the RCCL bucket all-reduces even at world size 1 (reducer/overlap mechanics check)")
     ap.add_argument("--nbatches", type=int, default=4, help="distinct synthetic batches cycled")
@@ -73,7 +84,19 @@ def parse():
                          "(DDP.overlap_optimizer) instead of after it")
     ap.add_argument("--dtype", default=None, choices=[None, "fp32", "bf16"],
                     help="simplenet compute dtype (default fp32, the reference's); resnet50/gpt2 are bf16")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the benchmark measures in runs of its own: "
+                         "at world size > 1 the instrumented per-bucket communication step ('buckets').  A plain "
+                         "run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed step computes as DIR/<name>.npy (float32): loss, "
+                         "and fixed seeded samples of the updated parameters and floating buffers (rank 0; at most "
+                         "64 MB in all).  The step is run once more, untimed, on the last timed step's batch from the "
+                         "seeded initial state, so two runs or two builds compare array for array")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (the number of timed steps)")
+    return args
 
 
 def main():
@@ -176,6 +199,11 @@ def main():
             p.grad = None  # buckets re-zeroed at next forward
         return loss
 
+    if args.dump_outputs:
+        if args.graph:
+            raise SystemExit("--dump-outputs: not with --graph (the captured step reads the bf16 weight shadows "
+                             "directly; restoring the seeded weights would leave them stale)")
+        state0 = _snapshot(model)  # the seeded state, before any step
     for i in range(args.warmup):
         step(i)
     if world > 1:  # after warm-up: the adaptive CU budget decided from measured comm (parallel/ddp.py)
@@ -201,8 +229,16 @@ def main():
     dt = t.item()
     ms = 1000.0 * dt / args.steps
     value = samples_per_step * world * args.steps / dt
+    last_loss = float(loss.item())
+    if args.dump_outputs:
+        # The timed path once more, untimed, on the last timed step's batch, from the seeded state: see
+        # the module docstring for why the trained state itself cannot be compared between runs.
+        _restore(model, opt, state0)
+        dump_loss = step(args.warmup + args.steps - 1)
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, dump_loss, model, dev)
     extra = {}
-    if args.bucket_timing if args.bucket_timing is not None else world > 1:
+    if args.bucket_timing if args.bucket_timing is not None else (args.full and world > 1):
         # one extra (untimed) step with per-bucket HIP events on the comm stream
         ddp.enable_timing(True)
         step(args.warmup + args.steps)
@@ -225,7 +261,7 @@ def main():
                 "vs_baseline": None,
                 "dtype": ("bf16" if args.model != "simplenet" else sdt) if dev.type == "cuda" else "fp32",
                 "data": "synthetic (device-resident, random)",
-                "config": cfg, "loss": float(loss.item())}
+                "config": cfg, "loss": last_loss}
         line.update(extra)
         print(json.dumps(line), flush=True)
     pdist.destroy_process_group()
@@ -270,6 +306,50 @@ def _graph_step(args, world, ddp, opt, model, xs, ys, fused_loss, num_classes, F
         return gloss
 
     return step
+
+
+DUMP_MAX_ELEMS = 8 << 20  # per array: 32 MB of float32 (loss + parameters + buffers stay under 64 MB)
+
+
+def _snapshot(model):
+    return [t.detach().clone() for t in (*model.parameters(), *model.buffers())]
+
+
+@torch.no_grad()
+def _restore(model, opt, snap):
+    """Put the model back in place (same storage: DDP's views and the optimizer's device table stay valid; the
+    version bump makes the layers re-cast their bf16 shadows) and zero the optimizer's state, step counters
+    included, so its next step is a first step."""
+    for t, s in zip((*model.parameters(), *model.buffers()), snap):
+        t.copy_(s)
+    for st in opt.state.values():
+        for v in st.values():
+            if torch.is_tensor(v):
+                v.zero_()
+
+
+def _dump_outputs(dirpath, loss, model, dev):
+    """What a caller of the timed step holds after it: its loss, and the model it updated.
+    Arrays larger than DUMP_MAX_ELEMS are reduced to a fixed sample (seeded index set, the same for every
+    build of the same model), taken on the host so the sample does not depend on a device generator."""
+    import numpy as np
+
+    _sync(dev)
+    os.makedirs(dirpath, exist_ok=True)
+
+    def flat(ts):
+        ts = [t.detach().reshape(-1).float().cpu() for t in ts]
+        v = torch.cat(ts).numpy() if ts else np.zeros(0, dtype=np.float32)
+        if v.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.RandomState(20240607).choice(v.size, DUMP_MAX_ELEMS, replace=False))
+            v = v[idx]
+        return np.ascontiguousarray(v, dtype=np.float32)
+
+    np.save(os.path.join(dirpath, "loss.npy"), loss.detach().float().cpu().reshape(1).numpy())
+    np.save(os.path.join(dirpath, "params.npy"), flat(list(model.parameters())))
+    bufs = [b for b in model.buffers() if b.is_floating_point()]  # BN running statistics
+    if bufs:
+        np.save(os.path.join(dirpath, "buffers.npy"), flat(bufs))
 
 
 class _null:

@@ -466,6 +466,9 @@ std::vector<std::tuple<int64_t, double, double>> Reducer::last_timings() {
   std::vector<std::tuple<int64_t, double, double>> out;
   if (host_launch_ || !timed_done_ || !comm_ || (comm_->world() == 1 && !force_)) return out;
   HIP_CHECK(hipEventSynchronize(ev_done_));
+  // ev_bwd_end_ is on the compute stream: when every bucket was launched during backward, the comm
+  // stream (ev_done_) does not order it, and hipEventElapsedTime would report hipErrorNotReady
+  HIP_CHECK(hipEventSynchronize(ev_bwd_end_));
   for (size_t b = 0; b < buckets_.size(); ++b) {
     float ms = 0.f, rel = 0.f;
     HIP_CHECK(hipEventElapsedTime(&ms, ev_start_[b], ev_end_[b]));
