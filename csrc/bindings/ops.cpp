@@ -112,6 +112,9 @@ int dpe_optim_chunk_size();
 int dpe_optim_desc_bytes();
 int dpe_optim_step(int kind, const void* desc, const void* chunks, int nchunks, const float* hp, const float* steps,
                    hipStream_t st);
+int dpe_optim_grad_norm(const void* desc, const void* chunks, int nchunks, float* partials, float* out, const float* max_norm,
+                        float* hp, int ngroups, int skip, hipStream_t st);
+int dpe_optim_grad_scale(const void* desc, const void* chunks, int nchunks, const float* out, hipStream_t st);
 int dpe_layernorm_fwd(const void* x, int x_bf16, const float* w, const float* b, uint16_t* y, float* mean, float* rstd,
                       int64_t rows, int D, float eps, hipStream_t st);
 int dpe_layernorm_bwd_nblocks(int64_t rows);
@@ -1897,6 +1900,42 @@ void optim_step(int64_t kind, const Tensor& desc, const Tensor& chunks, const Te
            "optim_step");
 }
 
+static void check_optim_table(const Tensor& desc, const Tensor& chunks) {
+  CHECK_GPU(desc); CHECK_GPU(chunks);
+  TORCH_CHECK(chunks.scalar_type() == at::kInt && chunks.dim() == 2 && chunks.size(1) == 2, "chunks must be int32 [n,2]");
+  TORCH_CHECK(chunks.is_contiguous() && desc.is_contiguous(), "optimizer table must be contiguous");
+}
+
+// Global gradient norm over the (tensor, chunk) table: out = [total_norm, coef, ok, skipped steps]; with `hp`
+// (the optimizer's hyper-parameter rows, 12 floats per group) coef and ok also go into every row.
+void optim_grad_norm(const Tensor& desc, const Tensor& chunks, Tensor& partials, Tensor& out, const Tensor& max_norm,
+                     const c10::optional<Tensor>& hp, bool skip_nonfinite) {
+  check_optim_table(desc, chunks);
+  CHECK_GPU(partials); CHECK_F32(partials); CHECK_CONTIG(partials);
+  CHECK_GPU(out); CHECK_F32(out); CHECK_CONTIG(out);
+  CHECK_GPU(max_norm); CHECK_F32(max_norm);
+  TORCH_CHECK(partials.numel() >= chunks.size(0), "optim_grad_norm: one partial per chunk");
+  TORCH_CHECK(out.numel() >= 4 && max_norm.numel() >= 1, "optim_grad_norm: out needs 4 floats, max_norm 1");
+  int ngroups = 0;
+  if (hp.has_value()) {
+    CHECK_GPU((*hp)); CHECK_F32((*hp)); CHECK_CONTIG((*hp));
+    TORCH_CHECK(hp->numel() % 12 == 0, "optim_grad_norm: hp holds 12 floats per group");
+    ngroups = (int)(hp->numel() / 12);
+  }
+  CHECK_RC(dpe_optim_grad_norm(desc.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), fp(partials), fp(out), fp(max_norm),
+                               fpom(hp), ngroups, skip_nonfinite ? 1 : 0, cur_stream()),
+           "optim_grad_norm");
+}
+
+// In-place g *= out[1] (the coef optim_grad_norm left) over the table's gradients.
+void optim_grad_scale(const Tensor& desc, const Tensor& chunks, const Tensor& out) {
+  check_optim_table(desc, chunks);
+  CHECK_GPU(out); CHECK_F32(out); CHECK_CONTIG(out);
+  TORCH_CHECK(out.numel() >= 4, "optim_grad_scale: out needs 4 floats");
+  CHECK_RC(dpe_optim_grad_scale(desc.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), fp(out), cur_stream()),
+           "optim_grad_scale");
+}
+
 // -------------------------------------------------------------- LayerNorm
 // x [rows, D] (f32 or bf16) -> y bf16, mean/rstd f32 [rows]
 std::vector<Tensor> layernorm_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, double eps) {
@@ -2158,6 +2197,9 @@ void register_ops(pybind11::module& m) {
   m.def("embedding_fwd", &embedding_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe") = py::none());
   m.def("embedding_bwd", &embedding_bwd, py::arg("idx"), py::arg("dout"), py::arg("dwte"), py::arg("dwpe") = py::none());
   m.def("optim_step", &optim_step);
+  m.def("optim_grad_norm", &optim_grad_norm, py::arg("desc"), py::arg("chunks"), py::arg("partials"), py::arg("out"),
+        py::arg("max_norm"), py::arg("hp") = py::none(), py::arg("skip_nonfinite") = false);
+  m.def("optim_grad_scale", &optim_grad_scale, py::arg("desc"), py::arg("chunks"), py::arg("out"));
   m.def("optim_chunk_size", []() { return dpe_optim_chunk_size(); });
   m.def("optim_desc_bytes", []() { return dpe_optim_desc_bytes(); });
   m.def("layernorm_bwd_residual", &layernorm_bwd_residual, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),

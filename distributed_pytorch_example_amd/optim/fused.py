@@ -15,6 +15,12 @@ Per-parameter ``step`` counters live in one device tensor (each state's
 ``step`` is a 0-d view of it), so a whole training step can be captured in a
 hipGraph; ``lr`` and friends live in a device hyper-parameter block that the
 host rewrites only when a group's values change.
+
+Global-norm gradient clipping (``set_grad_clip``) is fused into the step: one
+extra read of the gradients produces the norm on the device, a one-block
+kernel turns it into the clip coefficient inside the hyper-parameter block,
+and the update kernel multiplies every gradient by it.  The gradients are not
+written back, the host is not involved, and the step still replays in a graph.
 """
 from __future__ import annotations
 
@@ -26,6 +32,12 @@ from ..ops._ext import ext
 from ..ops import _state
 
 _HP = 12
+_CLIP_BUF = 5  # device clip block: total_norm, coef, ok, skipped steps | max_norm
+
+
+def _pack_desc(p, g, s1, s2, sh, n, group, ti):
+    """One ``TensorDesc`` of csrc/kernels/optim.hip."""
+    return struct.pack("<QQQQQqii", p, g, s1, s2, sh, n, group, ti)
 
 
 class _FusedMixin:
@@ -42,6 +54,71 @@ class _FusedMixin:
         self._ov_open = False
         self._ov_done = set()
         self._ov_cache = {}
+        self._clip_max = None  # set_grad_clip()
+        self._clip_skip = False
+        self._clip_buf = None  # allocated once per optimizer: the skipped-steps counter lives in it
+        self._clip_part = None  # one partial sum of squares per (tensor, chunk), allocated with the table
+        self._clip_ran = False
+
+    # ------------------------------------------------------ gradient clipping
+    def set_grad_clip(self, max_norm, *, skip_nonfinite: bool = False) -> None:
+        """Clip the gradients of ALL param groups together to the global 2-norm ``max_norm`` inside every
+        following ``step()`` (``torch.nn.utils.clip_grad_norm_(params, max_norm)`` followed by the step,
+        except that on GPU the gradients themselves are left as they are).  ``None`` turns it off.  With
+        ``skip_nonfinite`` a step whose gradient norm is inf/NaN changes nothing (parameters, states,
+        shadows and ``step`` counters) and is counted in ``skipped_steps``.  Not part of ``state_dict()``."""
+        if max_norm is None:
+            if skip_nonfinite:
+                raise ValueError("set_grad_clip: skip_nonfinite needs a max_norm")
+        else:
+            max_norm = float(max_norm)
+            if not max_norm > 0.0:
+                raise ValueError(f"set_grad_clip: max_norm must be > 0, got {max_norm}")
+            if self._ov_stream is not None:
+                raise RuntimeError("set_grad_clip: this optimizer steps per bucket during backward "
+                                   "(DDP.overlap_optimizer), before the global gradient norm exists")
+        if (max_norm is None) != (self._clip_max is None) or bool(skip_nonfinite) != self._clip_skip:
+            # mode change: the next step rebuilds the table (scratch) and rewrites the hp rows (coef/ok = 1.0)
+            self._tab = None
+            self._tab_key = None
+            self._hp_key = None
+        self._clip_max, self._clip_skip = max_norm, bool(skip_nonfinite)
+        if max_norm is not None and self._clip_buf is not None:
+            self._clip_buf[4].fill_(max_norm)  # a device scalar, like lr: a captured step picks it up
+
+    def _clip_scratch(self):
+        if self._clip_buf is None:
+            self._clip_buf = torch.zeros(_CLIP_BUF, dtype=torch.float32, device=self._all_params()[0].device)
+            if self._clip_max is not None:
+                self._clip_buf[4].fill_(self._clip_max)
+        return self._clip_buf
+
+    @property
+    def grad_norm(self):
+        """0-d fp32 tensor on the parameters' device: the gradient norm the last clipped step saw (before
+        clipping).  ``None`` before the first clipped step.  Reading it does not synchronise."""
+        return self._clip_buf[0] if self._clip_ran else None
+
+    @property
+    def skipped_steps(self):
+        """0-d fp32 counter on the parameters' device: steps skipped for a non-finite gradient norm."""
+        return self._clip_scratch()[3]
+
+    @torch.no_grad()
+    def _cpu_clip(self) -> bool:
+        """torch's own clip on the optimizer's parameters; False when the step is to be skipped."""
+        if self._clip_max is None:
+            return True
+        params = self._all_params()
+        buf = self._clip_scratch()
+        norm = torch.nn.utils.get_total_norm([p.grad for p in params if p.grad is not None])
+        buf[0].copy_(norm)
+        self._clip_ran = True
+        if self._clip_skip and not bool(torch.isfinite(norm)):
+            buf[3].add_(1.0)
+            return False
+        torch.nn.utils.clip_grads_with_norm_(params, self._clip_max, norm)
+        return True
 
     def _all_params(self):
         return [p for g in self.param_groups for p in g["params"]]
@@ -108,9 +185,9 @@ class _FusedMixin:
             if sh is not None and getattr(p, "_dpe_shadow_ver", -1) != p._version:
                 sh = None  # stale shadow: let the layer re-cast it
             self._ti[id(p)] = ti
-            desc += struct.pack("<QQQQQqii", p.data_ptr(), p.grad.data_ptr(), s1.data_ptr() if s1 is not None else 0,
-                                s2.data_ptr() if s2 is not None else 0, sh.data_ptr() if sh is not None else 0,
-                                p.numel(), gi_of[id(p)], ti)
+            desc += _pack_desc(p.data_ptr(), p.grad.data_ptr(), s1.data_ptr() if s1 is not None else 0,
+                               s2.data_ptr() if s2 is not None else 0, sh.data_ptr() if sh is not None else 0,
+                               p.numel(), gi_of[id(p)], ti)
             for c in range((p.numel() + chunk - 1) // chunk):
                 chunks.append((ti, c))
         assert len(desc) == C.optim_desc_bytes() * len(params), "TensorDesc ABI mismatch"
@@ -120,6 +197,9 @@ class _FusedMixin:
         self._tab = (d, ck)
         self._chunks_host = chunks
         self._ov_cache = {}
+        if self._clip_max is not None:
+            self._clip_part = torch.empty(max(len(chunks), 1), dtype=torch.float32, device=dev)
+            self._clip_scratch()
 
     def _key(self):
         ks = []
@@ -219,8 +299,15 @@ class _FusedMixin:
                 self._build_table()
                 self._tab_key = key
             self._write_hp()
-        self._steps.add_(1.0)
         d, ck = self._tab
+        if self._clip_max is not None:
+            # norm -> coef (and ok) into the hp rows, all on the device; a skipped step advances no counter
+            buf = self._clip_buf
+            ext().optim_grad_norm(d, ck, self._clip_part, buf, buf[4:], self._hp, self._clip_skip)
+            self._clip_ran = True
+            self._steps.add_(buf[2] if self._clip_skip else 1.0)
+        else:
+            self._steps.add_(1.0)
         ext().optim_step(self._kind, d, ck, self._hp, self._steps)
         _state.after_optimizer_step()
 
@@ -247,7 +334,7 @@ class Adam(_FusedMixin, torch.optim.Adam):
     def _hp_row(self, g):
         flags = (2 if g.get("maximize", False) else 0) | (4 if (self._decoupled or g.get("decoupled_weight_decay", False)) else 0)
         b1, b2 = g["betas"]
-        return [_lr(g), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), float(flags), 1.0] + [0.0] * (_HP - 7)
+        return [_lr(g), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), float(flags), 1.0, 1.0, 1.0] + [0.0] * (_HP - 9)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -258,6 +345,8 @@ class Adam(_FusedMixin, torch.optim.Adam):
         if self._use_fused():
             self._fused_step()
             return loss
+        if not self._cpu_clip():
+            return None
         return super().step()
 
 
@@ -282,8 +371,8 @@ class SGD(_FusedMixin, torch.optim.SGD):
 
     def _hp_row(self, g):
         flags = (1 if g["nesterov"] else 0) | (2 if g.get("maximize", False) else 0)
-        return [_lr(g), float(g["momentum"]), float(g["dampening"]), 0.0, float(g["weight_decay"]), float(flags), 1.0] + [
-            0.0] * (_HP - 7)
+        return [_lr(g), float(g["momentum"]), float(g["dampening"]), 0.0, float(g["weight_decay"]), float(flags), 1.0, 1.0, 1.0] + [
+            0.0] * (_HP - 9)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -294,4 +383,6 @@ class SGD(_FusedMixin, torch.optim.SGD):
         if self._use_fused():
             self._fused_step()
             return loss
+        if not self._cpu_clip():
+            return None
         return super().step()

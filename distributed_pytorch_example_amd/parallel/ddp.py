@@ -50,6 +50,13 @@ Design (MI355X-first, not a port of c10d::Reducer):
   post-accumulate hooks fired), so no backward kernel can read a weight the step rewrites.  The
   memory-bound update overlaps the compute-bound tail of backward instead of following it; ``opt.step()``
   then only joins the stream (and steps anything left).  Same math, same order per parameter.
+* **Gradient clipping** (``optimizer.set_grad_clip(max_norm)``): the fused optimizer's ``step()`` runs
+  after the end-of-backward callback has ordered the compute stream behind the last all-reduce, so the
+  global norm is taken over the AVERAGED buckets.  The norm kernels use no atomics and a fixed summation
+  order, so every rank derives bit for bit the same norm and clip coefficient from its (identical)
+  buckets and the replicas stay in lockstep without another collective.  It cannot be combined with
+  ``overlap_optimizer``: a bucket stepped during backward would be updated before the global norm
+  exists, so either order of asking for both raises ``RuntimeError``.
 """
 from __future__ import annotations
 
@@ -457,7 +464,7 @@ class DistributedDataParallel(nn.Module):
         (it joins the stream and steps whatever is left).  GPU only; with custom comm hooks or a host
         (gloo) transport at world > 1 the gradients are final only at the end of backward, so the
         overlap is refused there.  Gradient clipping / unscaling between backward and step cannot be
-        combined with it (the update has already run)."""
+        combined with it (the update has already run): an optimizer with ``set_grad_clip`` is refused."""
         if not enable:
             if self._ov_opt is not None:
                 self._ov_opt._ov_detach()
@@ -465,6 +472,9 @@ class DistributedDataParallel(nn.Module):
             return
         if not hasattr(optimizer, "_ov_bucket_step"):
             raise TypeError("overlap_optimizer needs one of the fused optimizers (distributed_pytorch_example_amd.optim)")
+        if getattr(optimizer, "_clip_max", None) is not None:
+            raise RuntimeError("overlap_optimizer: the optimizer clips by global gradient norm (set_grad_clip), "
+                               "which exists only after the whole backward")
         if not (self._params and self._params[0].is_cuda):
             raise RuntimeError("overlap_optimizer: GPU parameters only")
         if self.world_size > 1 and not self._native:

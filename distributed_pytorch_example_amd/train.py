@@ -52,6 +52,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "fp32 masters and gradients always)")
     p.add_argument("--optimizer", default=None, choices=[None, "adam", "adamw", "sgd"])
     p.add_argument("--weight-decay", type=float, default=0.0)
+    p.add_argument("--clip-grad-norm", type=float, default=None,
+                   help="clip gradients to this global 2-norm inside the optimizer step (default: off)")
+    p.add_argument("--skip-nonfinite-steps", action="store_true",
+                   help="with --clip-grad-norm: a step whose gradient norm is inf/NaN changes nothing")
     p.add_argument("--bucket-mb", type=float, default=None,
                    help="gradient bucket cap (default: the 7-link xGMI policy, parallel/buckets.py)")
     p.add_argument("--last-bucket-mb", type=float, default=None,
@@ -173,7 +177,12 @@ def _dtype_kw(args) -> dict:
 
 @record
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.skip_nonfinite_steps and args.clip_grad_norm is None:
+        parser.error("--skip-nonfinite-steps needs --clip-grad-norm")
+    if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
+        parser.error("--clip-grad-norm must be > 0")
     ensure_single_process_env()
     rank, world_size, local_rank = pdist.init_process_group(args.backend, comm_max_channels=args.comm_max_channels)
     logger.info(f"Initialized process group: rank={rank}, world_size={world_size}, local_rank={local_rank}")
@@ -201,7 +210,8 @@ def main(argv=None):
     logger.info(f"Dataset size: {len(train_dataset)}, batches per epoch: {len(train_loader)}")
 
     opt_name = args.optimizer or ("adam" if args.model == "simplenet" else ("sgd" if args.model.startswith("resnet") else "adamw"))
-    optimizer = build_optimizer(opt_name, model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    optimizer = build_optimizer(opt_name, model.parameters(), lr=args.lr, weight_decay=args.weight_decay,
+                                clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps)
 
     def criterion(out, tgt):
         return Fx.cross_entropy(out, tgt, num_classes)
@@ -240,6 +250,9 @@ def main(argv=None):
             logger.info(f"  Val Loss: {avg_val_loss:.4f}, Val Accuracy: {avg_val_accuracy:.2f}%")
             nb = min(len(train_loader), args.max_steps or len(train_loader))
             logger.info(f"  Throughput: {nb * args.batch_size * world_size / epoch_time:.1f} samples/s (incl. validation)")
+            if args.clip_grad_norm is not None and optimizer.grad_norm is not None:
+                gn, skipped = torch.stack([optimizer.grad_norm, optimizer.skipped_steps]).tolist()
+                logger.info(f"  Grad norm (last step): {gn:.4f}, skipped steps: {int(skipped)}")
             # no step heartbeat while rank 0 writes (RCCL async errors are still polled)
             with (watchdog.suspended() if watchdog is not None else _null()):
                 if avg_val_accuracy > best_accuracy:

@@ -1,0 +1,79 @@
+"""Worker of tests/test_grad_clip_rccl_world2_gpu.py: a small SimpleNet under DDP over real RCCL, rank-local
+data, 3 AdamW steps with a max_norm that clips on every step.  The norm is taken over the all-reduced
+(averaged) bucket views, so every rank must print the same norm bits and the same parameter hash.
+``reference()`` is the single-process run on the concatenated batch (imported by the test)."""
+import hashlib
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+WORLD = 2
+STEPS = 3
+MAX_NORM = 0.05
+BATCH = 8  # per rank
+
+
+def make_model(dev):
+    from distributed_pytorch_example_amd.models import get_model
+
+    torch.manual_seed(300)
+    return get_model("simplenet", input_size=64, hidden_size=128).to(dev).eval()  # eval: no dropout masks
+
+
+def rank_data(rank, step):
+    g = torch.Generator().manual_seed(1000 * (rank + 1) + step)
+    return torch.randn(BATCH, 64, generator=g), torch.randint(0, 10, (BATCH,), generator=g)
+
+
+def run(model, fwd, batches, dev):
+    """STEPS clipped steps; returns the norms' bit patterns."""
+    from distributed_pytorch_example_amd.ops import functional as Fx
+    from distributed_pytorch_example_amd.optim import build_optimizer
+
+    opt = build_optimizer("adamw", model.parameters(), lr=1e-2, weight_decay=1e-2, clip_grad_norm=MAX_NORM)
+    bits = []
+    for step in range(STEPS):
+        x, y = batches(step)
+        loss = Fx.cross_entropy(fwd(x.to(dev)), y.to(dev), 10)
+        loss.backward()
+        opt.step()
+        bits.append(opt.grad_norm.clone())
+        opt.zero_grad()
+    torch.cuda.synchronize()
+    return [int(b.view(torch.int32).item()) & 0xFFFFFFFF for b in bits]
+
+
+def reference(dev):
+    """One process, every rank's batch concatenated (the mean loss over it has the averaged gradient)."""
+    model = make_model(dev)
+
+    def batches(step):
+        xs, ys = zip(*(rank_data(r, step) for r in range(WORLD)))
+        return torch.cat(xs), torch.cat(ys)
+
+    return run(model, model, batches, dev)
+
+
+def main():
+    from distributed_pytorch_example_amd.parallel import DDP
+    from distributed_pytorch_example_amd.parallel import dist as pdist
+
+    rank, world, _ = pdist.init_process_group("rccl")
+    assert world == WORLD
+    dev = torch.device("cuda", 0)
+    model = make_model(dev)
+    ddp = DDP(model, bucket_cap_mb=0.25, first_bucket_mb=0.05)
+    assert ddp._native and ddp.reducer.world == world
+    bits = run(model, ddp, lambda step: rank_data(rank, step), dev)
+    h = hashlib.sha1()
+    for p in model.parameters():
+        h.update(p.detach().cpu().numpy().tobytes())
+    print(f"rank {rank} grad-clip result: params={h.hexdigest()} norms={','.join(f'{b:08x}' for b in bits)}", flush=True)
+    pdist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
