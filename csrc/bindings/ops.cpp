@@ -115,6 +115,14 @@ int dpe_optim_step(int kind, const void* desc, const void* chunks, int nchunks, 
 int dpe_optim_grad_norm(const void* desc, const void* chunks, int nchunks, float* partials, float* out, const float* max_norm,
                         float* hp, int ngroups, int skip, hipStream_t st);
 int dpe_optim_grad_scale(const void* desc, const void* chunks, int nchunks, const float* out, hipStream_t st);
+int dpe_optim_clip_coef(const float* partials, int nchunks, float* out, const float* max_norm, float* hp, int ngroups, int skip,
+                        hipStream_t st);
+int dpe_optim_trust_partials(int kind, const void* desc, const void* chunks, int nchunks, const float* hp, const float* steps,
+                             float* part_w, float* part_x, hipStream_t st);
+int dpe_optim_trust_ratio(int kind, const void* desc, int ntensors, const int* first_chunk, int nchunks, const float* part_w,
+                          const float* part_x, const float* hp, float* stats, hipStream_t st);
+int dpe_optim_trust_step(int kind, const void* desc, const void* chunks, int nchunks, const float* hp, const float* steps,
+                         const float* stats, hipStream_t st);
 int dpe_layernorm_fwd(const void* x, int x_bf16, const float* w, const float* b, uint16_t* y, float* mean, float* rstd,
                       int64_t rows, int D, float eps, hipStream_t st);
 int dpe_layernorm_bwd_nblocks(int64_t rows);
@@ -1936,6 +1944,79 @@ void optim_grad_scale(const Tensor& desc, const Tensor& chunks, const Tensor& ou
            "optim_grad_scale");
 }
 
+// The finishing kernel of optim_grad_norm alone, on `partials` that optim_trust_partials(kind 0) wrote.
+void optim_clip_coef(const Tensor& partials, int64_t nchunks, Tensor& out, const Tensor& max_norm, Tensor& hp,
+                     bool skip_nonfinite) {
+  CHECK_GPU(partials); CHECK_F32(partials); CHECK_CONTIG(partials);
+  CHECK_GPU(out); CHECK_F32(out); CHECK_CONTIG(out);
+  CHECK_GPU(max_norm); CHECK_F32(max_norm);
+  CHECK_GPU(hp); CHECK_F32(hp); CHECK_CONTIG(hp);
+  TORCH_CHECK(nchunks >= 0 && partials.numel() >= nchunks, "optim_clip_coef: one partial per chunk");
+  TORCH_CHECK(out.numel() >= 4 && max_norm.numel() >= 1, "optim_clip_coef: out needs 4 floats, max_norm 1");
+  TORCH_CHECK(hp.numel() % 12 == 0, "optim_clip_coef: hp holds 12 floats per group");
+  CHECK_RC(dpe_optim_clip_coef(fp(partials), (int)nchunks, fp(out), fp(max_norm), fp(hp), (int)(hp.numel() / 12),
+                               skip_nonfinite ? 1 : 0, cur_stream()),
+           "optim_clip_coef");
+}
+
+// LARS / LAMB (kind 0 / 1): the table checks of the other entry points plus the sizes of what the trust
+// kernels index per chunk (partials) and per tensor (first_chunk, stats).
+static int64_t check_trust_args(const char* what, const Tensor& desc, const Tensor& hp, const Tensor* steps_or_null,
+                                const Tensor& part_w, const Tensor& part_x, int64_t nchunks) {
+  CHECK_GPU(hp); CHECK_F32(hp); CHECK_CONTIG(hp);
+  CHECK_GPU(part_w); CHECK_F32(part_w); CHECK_CONTIG(part_w);
+  CHECK_GPU(part_x); CHECK_F32(part_x); CHECK_CONTIG(part_x);
+  const int64_t db = dpe_optim_desc_bytes();
+  TORCH_CHECK(desc.scalar_type() == at::kByte && desc.numel() % db == 0, what, ": desc is a byte tensor of whole TensorDescs");
+  const int64_t nt = desc.numel() / db;
+  TORCH_CHECK(hp.numel() >= 12 && hp.numel() % 12 == 0, what, ": hp holds 12 floats per group");
+  if (steps_or_null != nullptr) {
+    const Tensor& steps = *steps_or_null;
+    CHECK_GPU(steps); CHECK_F32(steps); CHECK_CONTIG(steps);
+    TORCH_CHECK(steps.numel() >= nt, what, ": one step counter per tensor");
+  }
+  TORCH_CHECK(part_w.numel() >= nchunks && part_x.numel() >= nchunks, what, ": one partial per chunk in both arrays");
+  return nt;
+}
+
+void optim_trust_partials(int64_t kind, const Tensor& desc, const Tensor& chunks, const Tensor& hp, const Tensor& steps,
+                          Tensor& part_w, Tensor& part_x) {
+  TORCH_CHECK(kind == 0 || kind == 1, "optim_trust_partials: kind 0 (LARS) or 1 (LAMB)");
+  check_optim_table(desc, chunks);
+  check_trust_args("optim_trust_partials", desc, hp, &steps, part_w, part_x, chunks.size(0));
+  CHECK_RC(dpe_optim_trust_partials((int)kind, desc.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), fp(hp), fp(steps),
+                                    fp(part_w), fp(part_x), cur_stream()),
+           "optim_trust_partials");
+}
+
+void optim_trust_ratio(int64_t kind, const Tensor& desc, const Tensor& first_chunk, int64_t nchunks, const Tensor& part_w,
+                       const Tensor& part_x, const Tensor& hp, Tensor& stats) {
+  TORCH_CHECK(kind == 0 || kind == 1, "optim_trust_ratio: kind 0 (LARS) or 1 (LAMB)");
+  CHECK_GPU(desc); CHECK_CONTIG(desc);
+  CHECK_GPU(first_chunk); CHECK_CONTIG(first_chunk);
+  CHECK_GPU(stats); CHECK_F32(stats); CHECK_CONTIG(stats);
+  TORCH_CHECK(nchunks >= 0, "optim_trust_ratio: nchunks");
+  const int64_t nt = check_trust_args("optim_trust_ratio", desc, hp, nullptr, part_w, part_x, nchunks);
+  TORCH_CHECK(first_chunk.scalar_type() == at::kInt && first_chunk.numel() == nt + 1,
+              "optim_trust_ratio: first_chunk is int32 [n_tensors + 1]");
+  TORCH_CHECK(stats.numel() >= 3 * nt, "optim_trust_ratio: stats holds 3 floats per tensor");
+  CHECK_RC(dpe_optim_trust_ratio((int)kind, desc.data_ptr(), (int)nt, (const int*)first_chunk.data_ptr(), (int)nchunks,
+                                 fp(part_w), fp(part_x), fp(hp), fp(stats), cur_stream()),
+           "optim_trust_ratio");
+}
+
+void optim_trust_step(int64_t kind, const Tensor& desc, const Tensor& chunks, const Tensor& hp, const Tensor& steps,
+                      const Tensor& stats) {
+  TORCH_CHECK(kind == 0 || kind == 1, "optim_trust_step: kind 0 (LARS) or 1 (LAMB)");
+  check_optim_table(desc, chunks);
+  CHECK_GPU(stats); CHECK_F32(stats); CHECK_CONTIG(stats);
+  const int64_t nt = check_trust_args("optim_trust_step", desc, hp, &steps, stats, stats, 0);
+  TORCH_CHECK(stats.numel() >= 3 * nt, "optim_trust_step: stats holds 3 floats per tensor");
+  CHECK_RC(dpe_optim_trust_step((int)kind, desc.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), fp(hp), fp(steps), fp(stats),
+                                cur_stream()),
+           "optim_trust_step");
+}
+
 // -------------------------------------------------------------- LayerNorm
 // x [rows, D] (f32 or bf16) -> y bf16, mean/rstd f32 [rows]
 std::vector<Tensor> layernorm_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, double eps) {
@@ -2200,6 +2281,11 @@ void register_ops(pybind11::module& m) {
   m.def("optim_grad_norm", &optim_grad_norm, py::arg("desc"), py::arg("chunks"), py::arg("partials"), py::arg("out"),
         py::arg("max_norm"), py::arg("hp") = py::none(), py::arg("skip_nonfinite") = false);
   m.def("optim_grad_scale", &optim_grad_scale, py::arg("desc"), py::arg("chunks"), py::arg("out"));
+  m.def("optim_clip_coef", &optim_clip_coef, py::arg("partials"), py::arg("nchunks"), py::arg("out"), py::arg("max_norm"),
+        py::arg("hp"), py::arg("skip_nonfinite") = false);
+  m.def("optim_trust_partials", &optim_trust_partials);
+  m.def("optim_trust_ratio", &optim_trust_ratio);
+  m.def("optim_trust_step", &optim_trust_step);
   m.def("optim_chunk_size", []() { return dpe_optim_chunk_size(); });
   m.def("optim_desc_bytes", []() { return dpe_optim_desc_bytes(); });
   m.def("layernorm_bwd_residual", &layernorm_bwd_residual, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),

@@ -26,7 +26,8 @@ struct TensorDesc {
 };
 
 // Per group, 12 floats: lr, beta1/momentum, beta2/dampening, eps, weight_decay,
-// flags(bitfield: 1 nesterov, 2 maximize, 4 decoupled wd), grad_scale, clip coef, step ok, pad...
+// flags(bitfield: 1 nesterov, 2 maximize, 4 decoupled wd), grad_scale, clip coef, step ok,
+// trust_coefficient (LARS) / trust ratio on-off (LAMB), trust_eps, pad.
 // The host initialises coef and ok to 1.0; grad_clip_coef_kernel overwrites them when clipping is on.
 constexpr int HP = 12;
 constexpr int HP_COEF = 7, HP_OK = 8;
@@ -191,21 +192,15 @@ DPE_DEVICE void chunk_loads(__amdgpu_buffer_rsrc_t rs, f32x4* v) {
 // 16-B group), read through a resource of the chunk's real byte count; other lanes read past it.
 DPE_DEVICE uint32_t tail_offset(int n4) { return threadIdx.x < 4 ? (uint32_t)(n4 + (int)threadIdx.x) * 4u : BUF_OOB; }
 
-// partials[b] = sum of squares of the gradient elements of table entry b (same grid as the update).
-__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
-                                                          float* __restrict__ partials) {
-  __shared__ float sh[4];
-  const int2 ck = chunks[blockIdx.x];
-  const TensorDesc d = td[ck.x];
-  const int64_t beg = (int64_t)ck.y * CHUNK;
-  const int n = (int)max((int64_t)0, min((int64_t)CHUNK, d.n - beg));
-  const float* g = d.g + beg;
+// The lane's share of the sum of squares of x[0, n) (n <= CHUNK; `al16`: x is 16-B aligned).  Shared by every
+// kernel that takes a chunk's norm, so they all sum in the same order.
+DPE_DEVICE float lane_sqsum(const float* x, bool al16, int n) {
   float s;
-  if (((uintptr_t)d.g & 15) == 0) {  // beg is a multiple of 16 B
+  if (al16) {
     const int n4 = n & ~3;
     f32x4 v[CLIP_STEPS];
-    chunk_loads(buf_rsrc(g, (uint32_t)n4 * 4u), v);
-    const float t = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(g, (uint32_t)n * 4u), tail_offset(n4), 0, 0));
+    chunk_loads(buf_rsrc(x, (uint32_t)n4 * 4u), v);
+    const float t = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(x, (uint32_t)n * 4u), tail_offset(n4), 0, 0));
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;  // 8 independent accumulators of <= 8 squares each
 #pragma unroll
     for (int k = 0; k < CLIP_STEPS; k += 2) {
@@ -218,13 +213,25 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const TensorDesc* __re
     float a0 = 0.f, a1 = 0.f;
     int j = threadIdx.x;
     for (; j + 256 < n; j += 512) {
-      const float x = g[j], y = g[j + 256];
-      a0 += x * x;
-      a1 += y * y;
+      const float x0 = x[j], x1 = x[j + 256];
+      a0 += x0 * x0;
+      a1 += x1 * x1;
     }
-    if (j < n) a0 += g[j] * g[j];
+    if (j < n) a0 += x[j] * x[j];
     s = a0 + a1;
   }
+  return s;
+}
+
+// partials[b] = sum of squares of the gradient elements of table entry b (same grid as the update).
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                          float* __restrict__ partials) {
+  __shared__ float sh[4];
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const int64_t beg = (int64_t)ck.y * CHUNK;
+  const int n = (int)max((int64_t)0, min((int64_t)CHUNK, d.n - beg));
+  float s = lane_sqsum(d.g + beg, ((uintptr_t)d.g & 15) == 0, n);  // beg is a multiple of 16 B
   s = warp_sum(s);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -293,6 +300,262 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const TensorDesc* __res
   }
 }
 
+// ------------------------------------------------------- layer-wise trust ratios (LARS / LAMB)
+// Every tensor's update is scaled by a ratio of two per-tensor 2-norms.  The norms reuse the clip machinery:
+// one partial per (tensor, chunk) block, no atomics, then a fixed-order fp64 sum -- here per tensor, over
+// the tensor's contiguous run of table entries [first_chunk[ti], first_chunk[ti + 1]).
+//   LARS: partials of (w, g)      -> ratio -> SGD update of ratio * (g' + wd * w)
+//   LAMB: phase 1 writes m, v and the partials of (w, u) -> ratio -> phase 2 recomputes u and writes w
+// hp slots: 9 trust_coefficient (LARS) / trust ratio on-off (LAMB), 10 trust_eps.
+// stats[ti] = (wn, gn or un, ratio), fp32.
+constexpr int HP_TRUST = 9, HP_TEPS = 10;
+
+// a * b that the compiler may not contract into a neighbouring add
+DPE_DEVICE float mul_nofuse(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// Thread 0 writes the block's two sums (fixed order: lane, wave butterfly, 4 waves).
+DPE_DEVICE void block_write2(float a, float b, float* __restrict__ pa, float* __restrict__ pb) {
+  __shared__ float sh[8];
+  a = warp_sum(a);
+  b = warp_sum(b);
+  if ((threadIdx.x & 63) == 0) {
+    sh[threadIdx.x >> 6] = a;
+    sh[4 + (threadIdx.x >> 6)] = b;
+  }
+  lds_barrier();  // LDS only: __syncthreads() would also wait for the block's last m / v stores
+  if (threadIdx.x == 0) {
+    pa[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    pb[blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+  }
+}
+
+// part_w[b] = sum p^2, part_g[b] = sum g^2 (the latter exactly grad_sqnorm_kernel's value: with clipping on,
+// grad_clip_coef_kernel runs on part_g and the gradients are read once for both norms).
+__global__ __launch_bounds__(256) void lars_sqnorm_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                          float* __restrict__ part_w, float* __restrict__ part_g) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const int64_t beg = (int64_t)ck.y * CHUNK;
+  const int n = (int)max((int64_t)0, min((int64_t)CHUNK, d.n - beg));
+  const float sw = lane_sqsum(d.p + beg, ((uintptr_t)d.p & 15) == 0, n);
+  const float sg = lane_sqsum(d.g + beg, ((uintptr_t)d.g & 15) == 0, n);
+  block_write2(sw, sg, part_w, part_g);
+}
+
+// SGD on d = ratio * (g' + wd * w), weight decay 0 afterwards.  Written as SgdRule plus one multiply that
+// stays a multiply, so ratio == 1 (trust_coefficient 0) is bit for bit sgd_kernel's update.
+struct LarsRule {
+  SgdRule r;
+  float ratio;
+  DPE_DEVICE LarsRule(const float* h, float step, float ratio_) : r(h, step), ratio(ratio_) {}
+  DPE_DEVICE void operator()(float& p, float g, float& b, float&) const {
+    g *= r.gscale;
+    if (r.maximize) g = -g;
+    if (r.wd != 0.f) g += r.wd * p;
+    g = mul_nofuse(ratio, g);
+    if (r.mom != 0.f) {
+      b = r.first ? g : r.mom * b + (1.f - r.damp) * g;
+      g = r.nesterov ? g + r.mom * b : b;
+    }
+    p -= r.lr * g;
+  }
+};
+
+__global__ __launch_bounds__(256) void lars_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                   const float* __restrict__ hp, const float* __restrict__ steps,
+                                                   const float* __restrict__ stats) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const float* h = hp + d.group * HP;
+  if (h[HP_OK] == 0.f) return;  // skipped step: uniform over the grid
+  optim_chunk<LarsRule, false>(d, LarsRule(h, steps[d.step_idx], stats[ck.x * 3 + 2]), ck.y);
+}
+
+struct LambRule {
+  float lr, b1, b2, eps, wd, gscale, rbc1, rbc2;
+  bool maximize;
+  DPE_DEVICE LambRule(const float* h, float step) {
+    lr = h[0]; b1 = h[1]; b2 = h[2]; eps = h[3]; wd = h[4];
+    maximize = (int)h[5] & 2;
+    gscale = h[6] * h[HP_COEF];
+    // 1 - b^t to a few ulp of the result: 1 - powf(b2, t) carries powf's absolute error (~6e-8 near 1)
+    // into a value of ~1e-3 * t, a relative 6e-5 / t that the update norm |u| would inherit whole.
+    rbc1 = -1.f / expm1f(step * log1pf(b1 - 1.f));
+    rbc2 = -1.f / expm1f(step * log1pf(b2 - 1.f));
+  }
+  DPE_DEVICE void moments(float g, float& m, float& v) const {
+    g *= gscale;
+    if (maximize) g = -g;
+    m = m + (1.f - b1) * (g - m);  // lerp, as torch
+    v = b2 * v + (1.f - b2) * g * g;
+  }
+  // The Adam update with the (coupled) weight decay inside.  Both phases call this on the same p, m, v;
+  // nothing in it is contracted with the caller's arithmetic, so both get the same bits.  It runs twice per
+  // element, so the bias corrections are multiplies by per-block reciprocals and the root and the quotient are
+  // the 1-ulp v_sqrt_f32 / v_rcp_f32: with IEEE divides and root the two phases spent ~70 VALU instructions per
+  // element, 40 % of the machine's issue rate at the streaming rate; a few 6e-8 roundings against the 1e-5
+  // the optimizers are held to.
+  DPE_DEVICE float update(float p, float m, float v) const {
+#pragma clang fp contract(off)
+    return (m * rbc1) * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v * rbc2) + eps) + wd * p;
+  }
+};
+
+// One (tensor, chunk) of LAMB.  PHASE 1: m, v <- g; sw += p^2, su += u^2 (the lane's share).  PHASE 2:
+// p -= lr_ratio * u, bf16 shadow.  The walk is optim_chunk's: 16-B steps pipelined one ahead through buffer
+// resources; the ragged end (or a whole chunk of a tensor that is not 16-B aligned) goes one element per
+// lane through resources clamped to the chunk, so no load or store is predicated there either.
+template <int PHASE>
+DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk, float lr_ratio, float& sw, float& su) {
+  const int64_t beg = (int64_t)chunk * CHUNK;
+  const int64_t end = min(d.n, beg + CHUNK);
+  const uintptr_t align = (uintptr_t)d.p | (uintptr_t)d.s1 | (uintptr_t)d.s2 | (PHASE == 1 ? (uintptr_t)d.g : 0);
+  const bool vec = (align & 15) == 0 && (PHASE == 1 || ((uintptr_t)d.shadow & 7) == 0);
+  const bool has_sh = PHASE == 2 && d.shadow != nullptr;
+  f32x4 aw = {0.f, 0.f, 0.f, 0.f}, au = aw;
+  int64_t i = beg;
+  if (vec) {
+    const int64_t vend = beg + ((end - beg) & ~(int64_t)1023);
+    const int nsteps = (int)((vend - beg) >> 10);
+    const uint32_t bytes = (uint32_t)((vend - beg) * 4);  // <= 64 KiB (CHUNK)
+    const __amdgpu_buffer_rsrc_t prs = buf_rsrc(d.p + beg, bytes), mrs = buf_rsrc(d.s1 + beg, bytes);
+    const __amdgpu_buffer_rsrc_t vrs = buf_rsrc(d.s2 + beg, bytes);
+    const __amdgpu_buffer_rsrc_t grs = buf_rsrc(PHASE == 1 ? d.g + beg : nullptr, PHASE == 1 ? bytes : 0u);
+    const __amdgpu_buffer_rsrc_t srs = buf_rsrc(has_sh ? d.shadow + beg : nullptr, has_sh ? bytes / 2 : 0u);
+    auto ld = [](__amdgpu_buffer_rsrc_t r, uint32_t o) {
+      return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, o, 0, 0));
+    };
+    const uint32_t lo = threadIdx.x * 16u;
+    f32x4 pn = ld(prs, lo), mn = ld(mrs, lo), vn = ld(vrs, lo), gn = pn;
+    if (PHASE == 1) gn = ld(grs, lo);
+    for (int k = 0; k < nsteps; ++k) {
+      f32x4 p = pn, m = mn, v = vn;
+      const f32x4 g = gn;
+      const uint32_t o = lo + (uint32_t)k * 4096u, on = k + 1 < nsteps ? o + 4096u : o;
+      pn = ld(prs, on);
+      if (PHASE == 1) gn = ld(grs, on);
+      mn = ld(mrs, on);
+      vn = ld(vrs, on);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float me = m[e], ve = v[e];
+        if (PHASE == 1) rule.moments(g[e], me, ve);
+        const float u = rule.update(p[e], me, ve);
+        if (PHASE == 1) {
+          m[e] = me; v[e] = ve;
+          aw[e] += p[e] * p[e];
+          au[e] += u * u;
+        } else {
+          p[e] -= lr_ratio * u;
+        }
+      }
+      if (PHASE == 1) {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), mrs, o, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), vrs, o, 0, 0);
+      } else {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, p), prs, o, 0, 0);
+        u32x2 sh;
+        sh[0] = pack_bf2(p[0], p[1]);
+        sh[1] = pack_bf2(p[2], p[3]);
+        __builtin_amdgcn_raw_buffer_store_b64(sh, srs, o >> 1, 0, 0);
+      }
+    }
+    i = vend;
+  }
+  const uint32_t tb = (uint32_t)((end - i) * 4);  // <= 64 KiB
+  const int nt = (int)((end - i + 255) >> 8);
+  const __amdgpu_buffer_rsrc_t prs = buf_rsrc(d.p + i, tb), mrs = buf_rsrc(d.s1 + i, tb), vrs = buf_rsrc(d.s2 + i, tb);
+  const __amdgpu_buffer_rsrc_t grs = buf_rsrc(PHASE == 1 ? d.g + i : nullptr, PHASE == 1 ? tb : 0u);
+  const __amdgpu_buffer_rsrc_t srs = buf_rsrc(has_sh ? d.shadow + i : nullptr, has_sh ? tb / 2 : 0u);
+  auto ld1 = [](__amdgpu_buffer_rsrc_t r, uint32_t o) {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0));
+  };
+  float tw = 0.f, tu = 0.f;
+  for (int k = 0; k < nt; ++k) {
+    const uint32_t o = ((uint32_t)k * 256u + threadIdx.x) * 4u;  // past tb: reads 0, the stores are dropped
+    float p = ld1(prs, o), m = ld1(mrs, o), v = ld1(vrs, o);
+    if (PHASE == 1) {
+      rule.moments(ld1(grs, o), m, v);
+      const float u = rule.update(p, m, v);
+      tw += p * p;
+      tu += o < tb ? u * u : 0.f;  // (0 / (0 + eps) is NaN at eps == 0)
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m), mrs, o, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), vrs, o, 0, 0);
+    } else {
+      p -= lr_ratio * rule.update(p, m, v);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(p), prs, o, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b16(f2bf(p), srs, o >> 1, 0, 0);
+    }
+  }
+  sw = ((aw[0] + aw[1]) + (aw[2] + aw[3])) + tw;
+  su = ((au[0] + au[1]) + (au[2] + au[3])) + tu;
+}
+
+__global__ __launch_bounds__(256) void lamb_phase1_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                          const float* __restrict__ hp, const float* __restrict__ steps,
+                                                          float* __restrict__ part_w, float* __restrict__ part_u) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const float* h = hp + d.group * HP;
+  if (h[HP_OK] == 0.f) return;  // skipped step: m and v stay as they are (uniform over the grid)
+  float sw, su;
+  lamb_chunk<1>(d, LambRule(h, steps[d.step_idx]), ck.y, 0.f, sw, su);
+  block_write2(sw, su, part_w, part_u);
+}
+
+__global__ __launch_bounds__(256) void lamb_phase2_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                          const float* __restrict__ hp, const float* __restrict__ steps,
+                                                          const float* __restrict__ stats) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const float* h = hp + d.group * HP;
+  if (h[HP_OK] == 0.f) return;
+  float sw, su;
+  lamb_chunk<2>(d, LambRule(h, steps[d.step_idx]), ck.y, h[0] * stats[ck.x * 3 + 2], sw, su);
+}
+
+// One wave per tensor: lane l sums partials first + l, first + l + 64, ... in fp64, then a butterfly.  Of
+// ResNet-50's 161 tensors the largest has 144 chunks and of GPT-2-small's 148 all but the embedding (2356)
+// have at most 144, most a handful: a 256-lane block would keep three waves idle behind a barrier, and the
+// launch is a latency-bound grid of ~150 waves either way.
+template <bool LAMB>
+__global__ __launch_bounds__(64) void trust_ratio_kernel(const TensorDesc* __restrict__ td, const int* __restrict__ first_chunk,
+                                                         int nchunks, const float* __restrict__ part_w,
+                                                         const float* __restrict__ part_x, const float* __restrict__ hp,
+                                                         float* __restrict__ stats) {
+  const int ti = blockIdx.x;
+  const float* h = hp + td[ti].group * HP;
+  if (h[HP_OK] == 0.f) return;  // skipped step: the stats of the last real step stay
+  const int c0 = max(first_chunk[ti], 0), c1 = min(first_chunk[ti + 1], nchunks);
+  double a = 0.0, b = 0.0;
+  for (int c = c0 + (int)threadIdx.x; c < c1; c += 64) {
+    a += (double)part_w[c];
+    b += (double)part_x[c];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o, 64);
+    b += __shfl_xor(b, o, 64);
+  }
+  if (threadIdx.x == 0) {
+    const float wn = (float)sqrt(a);
+    float xn = (float)sqrt(b), ratio = 1.f;
+    if (LAMB) {
+      if (h[HP_TRUST] != 0.f && wn > 0.f && xn > 0.f) ratio = wn / xn;
+    } else {
+      xn *= h[6] * h[HP_COEF];  // the norm of the clipped gradient
+      const float tc = h[HP_TRUST];
+      if (tc > 0.f && wn > 0.f && xn > 0.f) ratio = tc * wn / (xn + h[4] * wn + h[HP_TEPS]);
+    }
+    stats[ti * 3 + 0] = wn;
+    stats[ti * 3 + 1] = xn;
+    stats[ti * 3 + 2] = ratio;
+  }
+}
+
 }  // namespace dpe
 
 using namespace dpe;
@@ -320,6 +583,53 @@ extern "C" int dpe_optim_grad_norm(const void* desc, const void* chunks, int nch
                        partials);
   hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, nchunks > 0 ? nchunks : 0, out,
                      max_norm, hp, ngroups, skip);
+  return 0;
+}
+
+// The one-block finishing kernel alone, on partials something else produced (LARS: its own partials kernel).
+extern "C" int dpe_optim_clip_coef(const float* partials, int nchunks, float* out, const float* max_norm, float* hp,
+                                   int ngroups, int skip, hipStream_t st) {
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, st, partials, nchunks > 0 ? nchunks : 0, out, max_norm, hp,
+                     ngroups, skip);
+  return 0;
+}
+
+// Trust-ratio steps.  kind: 0 LARS, 1 LAMB.
+// partials: LARS part_w = sum p^2, part_x = sum g^2; LAMB phase 1 (writes m, v; part_x = sum u^2).
+extern "C" int dpe_optim_trust_partials(int kind, const void* desc, const void* chunks, int nchunks, const float* hp,
+                                        const float* steps, float* part_w, float* part_x, hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  if (kind == 0)
+    hipLaunchKernelGGL(lars_sqnorm_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks,
+                       part_w, part_x);
+  else
+    hipLaunchKernelGGL(lamb_phase1_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp,
+                       steps, part_w, part_x);
+  return 0;
+}
+
+extern "C" int dpe_optim_trust_ratio(int kind, const void* desc, int ntensors, const int* first_chunk, int nchunks,
+                                     const float* part_w, const float* part_x, const float* hp, float* stats, hipStream_t st) {
+  if (ntensors <= 0) return 0;
+  if (kind == 0)
+    hipLaunchKernelGGL(trust_ratio_kernel<false>, dim3(ntensors), dim3(64), 0, st, (const TensorDesc*)desc, first_chunk, nchunks,
+                       part_w, part_x, hp, stats);
+  else
+    hipLaunchKernelGGL(trust_ratio_kernel<true>, dim3(ntensors), dim3(64), 0, st, (const TensorDesc*)desc, first_chunk, nchunks,
+                       part_w, part_x, hp, stats);
+  return 0;
+}
+
+// The update: LARS's SGD on ratio * (g' + wd * w), or LAMB phase 2.
+extern "C" int dpe_optim_trust_step(int kind, const void* desc, const void* chunks, int nchunks, const float* hp,
+                                    const float* steps, const float* stats, hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  if (kind == 0)
+    hipLaunchKernelGGL(lars_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp, steps,
+                       stats);
+  else
+    hipLaunchKernelGGL(lamb_phase2_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp,
+                       steps, stats);
   return 0;
 }
 

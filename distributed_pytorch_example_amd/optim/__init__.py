@@ -1,19 +1,45 @@
 import torch
 
-from .fused import SGD, Adam, AdamW, _CLIP_BUF, _pack_desc
+from .fused import LAMB, LARS, SGD, Adam, AdamW, _CLIP_BUF, _pack_desc
 
-__all__ = ["SGD", "Adam", "AdamW", "build_optimizer", "clip_grad_norm_"]
+__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "build_optimizer", "clip_grad_norm_"]
+
+
+def _trust_groups(params, weight_decay, off):
+    """A flat parameter list becomes two groups: matrices / filters keep the weight decay and the trust
+    ratio, tensors with ndim <= 1 (biases, BatchNorm / LayerNorm gains) get neither (``off``).  Param groups
+    the caller made are kept as they are."""
+    params = list(params)
+    if not params or isinstance(params[0], dict):
+        return params
+    big = [p for p in params if p.ndim > 1]
+    small = [p for p in params if p.ndim <= 1]
+    groups = [{"params": big}] if big else []
+    if small:
+        groups.append({"params": small, "weight_decay": 0.0, **off})
+    return groups
 
 
 def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, momentum: float = 0.9, *,
-                    clip_grad_norm=None, skip_nonfinite: bool = False):
+                    clip_grad_norm=None, skip_nonfinite: bool = False, trust_coefficient=None):
     name = name.lower()
+    if trust_coefficient is not None and name not in ("lars", "lamb"):
+        raise ValueError(f"trust_coefficient is for lars / lamb, not {name!r}")
     if name == "adam":
         opt = Adam(params, lr=lr, weight_decay=weight_decay)
     elif name == "adamw":
         opt = AdamW(params, lr=lr, weight_decay=weight_decay)
     elif name == "sgd":
         opt = SGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+    elif name == "lars":
+        opt = LARS(_trust_groups(params, weight_decay, {"trust_coefficient": 0.0}), lr=lr, momentum=momentum,
+                   weight_decay=weight_decay, trust_coefficient=1e-3 if trust_coefficient is None else trust_coefficient)
+    elif name == "lamb":
+        # LAMB's ratio has no coefficient: trust_coefficient=0 turns it off, anything else leaves it on
+        if trust_coefficient is not None and not trust_coefficient >= 0.0:
+            raise ValueError(f"Invalid trust_coefficient: {trust_coefficient}")
+        opt = LAMB(_trust_groups(params, weight_decay, {"trust_ratio": False}), lr=lr, weight_decay=weight_decay,
+                   trust_ratio=trust_coefficient is None or trust_coefficient > 0)
     else:
         raise ValueError(f"unknown optimizer {name!r}")
     if clip_grad_norm is not None or skip_nonfinite:

@@ -1,4 +1,4 @@
-"""Fused multi-tensor optimizers (Adam / AdamW / SGD-momentum).
+"""Fused multi-tensor optimizers (Adam / AdamW / SGD-momentum, and the layer-wise LARS / LAMB).
 
 Drop-in subclasses of the torch optimizers: identical constructor arguments,
 identical ``state_dict()`` schema (so checkpoints interchange with the
@@ -41,7 +41,9 @@ def _pack_desc(p, g, s1, s2, sh, n, group, ti):
 
 
 class _FusedMixin:
-    _kind = 0  # 0 adam, 1 sgd
+    _kind = 0  # 0 adam, 1 sgd: the state schema and the plain update kernel
+    _trust = None  # layer-wise trust ratio: None, 0 LARS, 1 LAMB (the kind of the ext().optim_trust_* calls)
+    _trust_defaults = {}  # the per-group keys a trust optimizer adds to torch's
 
     def _fused_init(self):
         self._tab = None
@@ -59,6 +61,9 @@ class _FusedMixin:
         self._clip_buf = None  # allocated once per optimizer: the skipped-steps counter lives in it
         self._clip_part = None  # one partial sum of squares per (tensor, chunk), allocated with the table
         self._clip_ran = False
+        self._trust_tab = None  # (first_chunk, part_w, part_x), allocated with the table
+        self._trust_stats = None
+        self._trust_ran = False
 
     # ------------------------------------------------------ gradient clipping
     def set_grad_clip(self, max_norm, *, skip_nonfinite: bool = False) -> None:
@@ -200,6 +205,19 @@ class _FusedMixin:
         if self._clip_max is not None:
             self._clip_part = torch.empty(max(len(chunks), 1), dtype=torch.float32, device=dev)
             self._clip_scratch()
+        if self._trust is not None:
+            # a tensor's chunks are contiguous in the table: tensor ti owns entries [first[ti], first[ti + 1])
+            first, ti_next = [], 0
+            for i, (ti, _) in enumerate(chunks):
+                while ti_next <= ti:
+                    first.append(i)
+                    ti_next += 1
+            first += [len(chunks)] * (len(params) + 1 - len(first))
+            self._trust_tab = (torch.tensor(first, dtype=torch.int32).to(dev),
+                               torch.zeros(max(len(chunks), 1), dtype=torch.float32, device=dev),
+                               torch.zeros(max(len(chunks), 1), dtype=torch.float32, device=dev))
+            if self._trust_stats is None or self._trust_stats.shape[0] != len(params) or self._trust_stats.device != dev:
+                self._trust_stats = torch.zeros(len(params), 3, dtype=torch.float32, device=dev)
 
     def _key(self):
         ks = []
@@ -218,6 +236,9 @@ class _FusedMixin:
         allocator): drop the device table and the step counters so the next fused step rebuilds both
         from the loaded state instead of touching freed memory."""
         super().load_state_dict(state_dict)
+        for g in self.param_groups:  # a stock torch.optim state has no trust keys: keep this optimizer's defaults
+            for k, v in self._trust_defaults.items():
+                g.setdefault(k, v)
         self._steps = None
         self._tab = None
         self._tab_key = None
@@ -239,6 +260,9 @@ class _FusedMixin:
 
     # -------------------------------------------- optimizer in backward (DDP.overlap_optimizer)
     def _ov_attach(self, stream):
+        if self._trust is not None:
+            raise RuntimeError("overlap_optimizer: a layer-wise trust ratio needs every tensor's whole gradient and a "
+                               "grid-wide step between backward and the update; it cannot step per bucket")
         self._ov_stream, self._ov_open, self._ov_done = stream, False, set()
 
     def _ov_detach(self):
@@ -300,6 +324,10 @@ class _FusedMixin:
                 self._tab_key = key
             self._write_hp()
         d, ck = self._tab
+        if self._trust is not None:
+            self._trust_step(d, ck)
+            _state.after_optimizer_step()
+            return
         if self._clip_max is not None:
             # norm -> coef (and ok) into the hp rows, all on the device; a skipped step advances no counter
             buf = self._clip_buf
@@ -310,6 +338,56 @@ class _FusedMixin:
             self._steps.add_(1.0)
         ext().optim_step(self._kind, d, ck, self._hp, self._steps)
         _state.after_optimizer_step()
+
+    # ------------------------------------------------------ layer-wise trust ratios (LARS / LAMB)
+    def _trust_step(self, d, ck):
+        """partials -> per-tensor ratio -> update, all on the device (csrc/kernels/optim.hip).  LARS takes
+        the gradient's partials together with the weight's, and the clip coefficient from those; LAMB's
+        phase 1 needs the clipped gradient (and the advanced step counter), so the clip pair runs first."""
+        C = ext()
+        first, pw, px = self._trust_tab
+        nck = ck.size(0)
+        clip, buf = self._clip_max is not None, self._clip_buf
+        if self._trust == 0:
+            C.optim_trust_partials(0, d, ck, self._hp, self._steps, pw, px)
+            if clip:
+                C.optim_clip_coef(px, nck, buf, buf[4:], self._hp, self._clip_skip)
+        elif clip:
+            C.optim_grad_norm(d, ck, self._clip_part, buf, buf[4:], self._hp, self._clip_skip)
+        if clip:
+            self._clip_ran = True
+        self._steps.add_(buf[2] if clip and self._clip_skip else 1.0)  # a skipped step advances no counter
+        if self._trust == 1:
+            C.optim_trust_partials(1, d, ck, self._hp, self._steps, pw, px)
+        C.optim_trust_ratio(self._trust, d, first, nck, pw, px, self._hp, self._trust_stats)
+        C.optim_trust_step(self._trust, d, ck, self._hp, self._steps, self._trust_stats)
+        self._trust_ran = True
+
+    @property
+    def trust_stats(self):
+        """fp32 ``[n_params, 3]`` on the parameters' device, rows in ``param_groups`` order: weight norm,
+        gradient norm (LARS, after clipping) or update norm (LAMB), trust ratio -- of the last step that
+        was not skipped.  ``None`` before the first step and for optimizers without a trust ratio.
+        Reading it does not synchronise."""
+        return self._trust_stats if self._trust_ran else None
+
+    def _group_trust_on(self, g) -> bool:
+        return False
+
+    def trust_on(self):
+        """bool ``[n_params]`` (host): whether the tensor's group applies a trust ratio."""
+        return torch.tensor([self._group_trust_on(g) for g in self.param_groups for _ in g["params"]], dtype=torch.bool)
+
+    def _set_trust_defaults(self, **kw):
+        self._trust_defaults = dict(kw)
+        self.defaults.update(kw)
+        for g in self.param_groups:
+            for k, v in kw.items():
+                g.setdefault(k, v)
+
+    def _cpu_stats(self, rows):
+        self._trust_stats = torch.tensor(rows, dtype=torch.float32).reshape(-1, 3)
+        self._trust_ran = True
 
 
 def _lr(g):
@@ -386,3 +464,141 @@ class SGD(_FusedMixin, torch.optim.SGD):
         if not self._cpu_clip():
             return None
         return super().step()
+
+
+class LARS(SGD):
+    """Layer-wise adaptive rate scaling (You, Gitman & Ginsburg 2017) on the fused SGD: per tensor
+
+        ratio = trust_coefficient * |w| / (|g'| + weight_decay * |w| + trust_eps)   (1 if a norm is 0 / NaN)
+        d     = ratio * (g' + weight_decay * w)
+
+    and then torch SGD's momentum / dampening / nesterov rule on ``d`` with weight decay 0.  ``g'`` is the
+    gradient after global-norm clipping (``set_grad_clip``) and ``maximize``.  ``trust_coefficient`` and
+    ``trust_eps`` are per-group keys; a group with ``trust_coefficient == 0`` is plain SGD.  The state keeps
+    SGD's schema, so a ``torch.optim.SGD`` state loads.  On GPU: one read of w and g for the partial sums,
+    one wave per tensor for the ratios, one update launch; no host work, graph-replayable."""
+
+    _trust = 0
+
+    def __init__(self, params, lr=1e-3, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False,
+                 trust_coefficient=1e-3, trust_eps=1e-8, *, maximize=False, **kw):
+        if not trust_coefficient >= 0.0:
+            raise ValueError(f"Invalid trust_coefficient: {trust_coefficient}")
+        if not trust_eps >= 0.0:
+            raise ValueError(f"Invalid trust_eps: {trust_eps}")
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                         nesterov=nesterov, maximize=maximize, **kw)
+        self._set_trust_defaults(trust_coefficient=float(trust_coefficient), trust_eps=float(trust_eps))
+        for g in self.param_groups:
+            if not (g["trust_coefficient"] >= 0.0 and g["trust_eps"] >= 0.0):
+                raise ValueError("Invalid trust_coefficient / trust_eps in a param group")
+
+    def _group_trust_on(self, g):
+        return g["trust_coefficient"] > 0
+
+    def _hp_row(self, g):
+        row = super()._hp_row(g)
+        row[9], row[10] = float(g["trust_coefficient"]), float(g["trust_eps"])
+        return row
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._use_fused():
+            self._fused_step()
+            return loss
+        if not self._cpu_clip():
+            return None
+        rows = []
+        for group in self.param_groups:
+            lr, mom, damp, wd = _lr(group), group["momentum"], group["dampening"], group["weight_decay"]
+            tc, te = group["trust_coefficient"], group["trust_eps"]
+            for p in group["params"]:
+                if p.grad is None:
+                    rows.append([float(p.norm()), 0.0, 1.0])
+                    continue
+                g = -p.grad if group.get("maximize", False) else p.grad
+                wn, gn = p.norm(), g.norm()
+                ratio = tc * wn / (gn + wd * wn + te) if (tc > 0 and wn > 0 and gn > 0) else torch.ones(())
+                rows.append([float(wn), float(gn), float(ratio)])
+                d = (g + wd * p) * ratio
+                st = self.state[p]
+                st["step"] = st.get("step", torch.zeros((), dtype=torch.float32)) + 1.0
+                if mom != 0:
+                    buf = st.get("momentum_buffer")
+                    if buf is None:
+                        buf = st["momentum_buffer"] = d.clone()
+                    else:
+                        buf.mul_(mom).add_(d, alpha=1.0 - damp)
+                    d = d.add(buf, alpha=mom) if group["nesterov"] else buf
+                p.add_(d, alpha=-lr)
+        self._cpu_stats(rows)
+        return loss
+
+
+class LAMB(Adam):
+    """LAMB (You et al. 2020) on the fused Adam machinery: with ``t`` the step counter after its increment,
+
+        m = lerp(m, g', 1 - b1),  v = b2 * v + (1 - b2) * g'^2
+        u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + weight_decay * w
+        w -= lr * (|w| / |u|) * u                                  (ratio 1 if a norm is 0 / NaN)
+
+    The weight decay sits inside ``u``, before the ratio (not AdamW's decoupled multiply).  ``trust_ratio`` is
+    a per-group key; a group with it off takes ``w -= lr * u``.  The state keeps Adam's schema, so a
+    ``torch.optim.AdamW`` state loads.  On GPU the step is two passes around the per-tensor ratio kernel:
+    phase 1 writes m, v and the partial sums of w^2 and u^2, phase 2 recomputes the same u and writes w."""
+
+    _trust = 1
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, trust_ratio=True, *,
+                 maximize=False, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize, **kw)
+        self._set_trust_defaults(trust_ratio=bool(trust_ratio))
+
+    def _group_trust_on(self, g):
+        return bool(g["trust_ratio"])
+
+    def _hp_row(self, g):
+        b1, b2 = g["betas"]
+        return [_lr(g), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), 2.0 if g.get("maximize", False) else 0.0,
+                1.0, 1.0, 1.0, 1.0 if g["trust_ratio"] else 0.0, 0.0, 0.0]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._use_fused():
+            self._fused_step()
+            return loss
+        if not self._cpu_clip():
+            return None
+        rows = []
+        for group in self.param_groups:
+            lr, (b1, b2), eps, wd = _lr(group), group["betas"], group["eps"], group["weight_decay"]
+            for p in group["params"]:
+                if p.grad is None:
+                    rows.append([float(p.norm()), 0.0, 1.0])
+                    continue
+                g = -p.grad if group.get("maximize", False) else p.grad
+                st = self.state[p]
+                if "exp_avg" not in st:
+                    st["step"] = torch.zeros((), dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] = st["step"] + 1.0
+                t = float(st["step"])
+                m, v = st["exp_avg"], st["exp_avg_sq"]
+                m.lerp_(g, 1.0 - b1)
+                v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+                u = (m / (1.0 - b1 ** t)) / ((v / (1.0 - b2 ** t)).sqrt() + eps) + wd * p
+                wn, un = p.norm(), u.norm()
+                ratio = wn / un if (group["trust_ratio"] and wn > 0 and un > 0) else torch.ones(())
+                rows.append([float(wn), float(un), float(ratio)])
+                p.add_(u * ratio, alpha=-lr)
+        self._cpu_stats(rows)
+        return loss

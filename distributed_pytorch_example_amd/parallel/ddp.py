@@ -464,7 +464,8 @@ class DistributedDataParallel(nn.Module):
         (it joins the stream and steps whatever is left).  GPU only; with custom comm hooks or a host
         (gloo) transport at world > 1 the gradients are final only at the end of backward, so the
         overlap is refused there.  Gradient clipping / unscaling between backward and step cannot be
-        combined with it (the update has already run): an optimizer with ``set_grad_clip`` is refused."""
+        combined with it (the update has already run): an optimizer with ``set_grad_clip`` is refused, and
+        so are ``optim.LARS`` / ``optim.LAMB``, whose per-tensor norms exist only after the whole backward."""
         if not enable:
             if self._ov_opt is not None:
                 self._ov_opt._ov_detach()
@@ -475,6 +476,9 @@ class DistributedDataParallel(nn.Module):
         if getattr(optimizer, "_clip_max", None) is not None:
             raise RuntimeError("overlap_optimizer: the optimizer clips by global gradient norm (set_grad_clip), "
                                "which exists only after the whole backward")
+        if getattr(optimizer, "_trust", None) is not None:
+            raise RuntimeError("overlap_optimizer: the optimizer scales every tensor by a layer-wise trust ratio "
+                               "(LARS / LAMB), whose norms exist only after the whole backward")
         if not (self._params and self._params[0].is_cuda):
             raise RuntimeError("overlap_optimizer: GPU parameters only")
         if self.world_size > 1 and not self._native:

@@ -50,7 +50,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dtype", default=None, choices=[None, "fp32", "bf16"],
                    help="compute dtype on the GPU (default: fp32 for simplenet as the reference, bf16 otherwise; "
                         "fp32 masters and gradients always)")
-    p.add_argument("--optimizer", default=None, choices=[None, "adam", "adamw", "sgd"])
+    p.add_argument("--optimizer", default=None, choices=[None, "adam", "adamw", "sgd", "lars", "lamb"])
+    p.add_argument("--trust-coefficient", type=float, default=None,
+                   help="--optimizer lars: the trust coefficient (default 1e-3); lamb: 0 turns the trust ratio off")
     p.add_argument("--weight-decay", type=float, default=0.0)
     p.add_argument("--clip-grad-norm", type=float, default=None,
                    help="clip gradients to this global 2-norm inside the optimizer step (default: off)")
@@ -183,6 +185,8 @@ def main(argv=None):
         parser.error("--skip-nonfinite-steps needs --clip-grad-norm")
     if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
         parser.error("--clip-grad-norm must be > 0")
+    if args.trust_coefficient is not None and args.optimizer not in ("lars", "lamb"):
+        parser.error("--trust-coefficient needs --optimizer lars or lamb")
     ensure_single_process_env()
     rank, world_size, local_rank = pdist.init_process_group(args.backend, comm_max_channels=args.comm_max_channels)
     logger.info(f"Initialized process group: rank={rank}, world_size={world_size}, local_rank={local_rank}")
@@ -211,7 +215,8 @@ def main(argv=None):
 
     opt_name = args.optimizer or ("adam" if args.model == "simplenet" else ("sgd" if args.model.startswith("resnet") else "adamw"))
     optimizer = build_optimizer(opt_name, model.parameters(), lr=args.lr, weight_decay=args.weight_decay,
-                                clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps)
+                                clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps,
+                                **({"trust_coefficient": args.trust_coefficient} if opt_name in ("lars", "lamb") else {}))
 
     def criterion(out, tgt):
         return Fx.cross_entropy(out, tgt, num_classes)
@@ -253,6 +258,12 @@ def main(argv=None):
             if args.clip_grad_norm is not None and optimizer.grad_norm is not None:
                 gn, skipped = torch.stack([optimizer.grad_norm, optimizer.skipped_steps]).tolist()
                 logger.info(f"  Grad norm (last step): {gn:.4f}, skipped steps: {int(skipped)}")
+            if getattr(optimizer, "trust_stats", None) is not None:
+                on = optimizer.trust_on()
+                if on.any():
+                    r = optimizer.trust_stats[:, 2].cpu()[on]
+                    logger.info(f"  Trust ratio (last step): min {r.min().item():.4g}, median {r.median().item():.4g}, "
+                                f"max {r.max().item():.4g}")
             # no step heartbeat while rank 0 writes (RCCL async errors are still polled)
             with (watchdog.suspended() if watchdog is not None else _null()):
                 if avg_val_accuracy > best_accuracy:
