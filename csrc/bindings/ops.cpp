@@ -22,7 +22,9 @@ int dpe_cu_reserve();  // comm.cpp: slots to leave to in-flight collectives
 int dpe_gram_blocks(int64_t M, int C);
 int64_t dpe_gram_ws_floats(int64_t M, int C);
 int dpe_gram(const uint16_t* x, const float* coef, const float* scoef, int64_t M, int C, float* ws, float* G, float* s,
-             hipStream_t st);
+             hipStream_t st, int sh, int sw);
+int dpe_gram_pilot(const uint16_t* x, int64_t M, int C, float* coef, hipStream_t st, int sh, int sw);
+int dpe_gram_u(const float* G, const uint16_t* w, int Cin, int Cout, float* u, hipStream_t st);
 int dpe_gram_coef(const float* G, const float* s, const uint16_t* w, int Cin, int Cout, int64_t M, const float* gamma,
                   const float* beta, float* rmean, float* rvar, float momentum, float eps, float* coef, float* u,
                   hipStream_t st);
@@ -355,7 +357,7 @@ void run_igemm(dpe::IgemmArgs& a, int aload, int bload, int epi, bool allow_spli
   static const bool dma_1x1 = [] { const char* e = getenv("DPE_WGRAD_DMA_1X1"); return !(e && e[0] == '0'); }();
   if (conv && epi == dpe::EPI_ATOMIC_F32 && aload == dpe::A_DENSE_M &&
       ((igemm_dma_on() && wgrad_dma_on() && bload == dpe::B_CONV_WGRAD) ||
-       (bload == dpe::B_DENSE_N && (a.b_coef || (dma_1x1 && igemm_dma_on()))))) {
+       (bload == dpe::B_DENSE_N && (a.b_coef || deterministic || (dma_1x1 && igemm_dma_on() && a.K % 32 == 0))))) {
     int bm = c.bm, bn = c.bn, splits = c.splits;
     {
       // ~3 resident 128x128 blocks per CU (4 fit): ResNet-50 step, alternating
@@ -1156,7 +1158,10 @@ void conv_wgrad(const Tensor& dy, const Tensor& x, Tensor& dw, std::vector<int64
   }
   const bool hgemm_1x1 = wgrad_hgemm_on() && is_pointwise(g) && a.K % 64 == 0 && g.K >= 256 && g.C >= 256 &&
                          g.K % 8 == 0 && g.C % 8 == 0;
-  if (overwrite && !hgemm_1x1)  // the accumulating kernels below: start from zeros
+  // a plain 1x1 below the persistent GEMM's widths with deterministic: the LDS-DMA weight grad's slab form
+  // (run_igemm handles overwrite there; outside that kernel's envelope it is an error)
+  const bool det_1x1 = deterministic && is_pointwise(g) && !hgemm_1x1 && !row;
+  if (overwrite && !hgemm_1x1 && !det_1x1)  // the accumulating kernels below: start from zeros
     TORCH_CHECK(hipMemsetAsync(dw.data_ptr(), 0, dw.numel() * sizeof(float), cur_stream()) == hipSuccess, "memset");
   if (row && (row_wgrad_on() || icoef)) {
     auto scratch = at::empty({dpe_wgrad3x3_rows_scratch(row_nb)}, dw.options());
@@ -1203,6 +1208,11 @@ void conv_wgrad(const Tensor& dy, const Tensor& x, Tensor& dw, std::vector<int64
     h.alpha = (float)alpha;
     h.conv = 2; h.conv_g = g; h.conv_smagic = (65536 + g.S - 1) / g.S;
     dpe_gemm::run_conv_wgrad(h, (hipStream_t)(uintptr_t)fin_stream);
+    return;
+  }
+  if (det_1x1) {
+    TORCH_CHECK(igemm_dma_on(), "conv_wgrad: a deterministic 1x1 weight grad needs the LDS-DMA kernel");
+    run_igemm(a, dpe::A_DENSE_M, dpe::B_DENSE_N, dpe::EPI_ATOMIC_F32, true, true, true, overwrite);
     return;
   }
   run_igemm(a, dpe::A_DENSE_M, is_pointwise(g) ? dpe::B_DENSE_N : dpe::B_CONV_WGRAD, dpe::EPI_ATOMIC_F32, true, true);
@@ -1290,9 +1300,13 @@ std::vector<Tensor> bn_bwd(const Tensor& dy, const c10::optional<Tensor>& y, con
 // G = a'^T a' [C][C] and s = [colsum(a'), mu] [2][C] of a' = a2 - mu, a2 = relu(x * coef[0] + coef[1]) (coef: the
 // BN's [4][C]) or x, centred on the pilot shift mu (bngram.hip relu_gauss_mean) of the BN coefficients
 // shift_coef (default: coef; neither: mu = 0).
-std::vector<Tensor> bn_gram(const Tensor& x, const c10::optional<Tensor>& coef, const c10::optional<Tensor>& shift_coef) {
+// stride2: x is an [N, H, W, C] image (even H, W) and the pass runs over its stride-2 subsample x[:, ::2, ::2, :],
+// the input pixels of a stride-2 1x1 conv, by row addressing (no copy).
+std::vector<Tensor> bn_gram(const Tensor& x, const c10::optional<Tensor>& coef, const c10::optional<Tensor>& shift_coef,
+                            bool stride2) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x);
-  const int64_t C = x.size(-1), M = x.numel() / C;
+  TORCH_CHECK(!stride2 || (x.dim() == 4 && x.size(1) % 2 == 0 && x.size(2) % 2 == 0), "bn_gram: stride2 needs [N, H, W, C], even H, W");
+  const int64_t C = x.size(-1), M = x.numel() / C / (stride2 ? 4 : 1);
   TORCH_CHECK(C == 64 || C == 128 || C == 256, "bn_gram: C must be 64, 128 or 256");
   if (coef.has_value() && coef->defined()) {
     CHECK_F32((*coef)); CHECK_CONTIG((*coef));
@@ -1308,7 +1322,8 @@ std::vector<Tensor> bn_gram(const Tensor& x, const c10::optional<Tensor>& coef, 
   auto fo = x.options().dtype(at::kFloat);
   Tensor ws = at::empty({dpe_gram_ws_floats(M, (int)C)}, fo);
   Tensor G = at::empty({C, C}, fo), sv = at::empty({2, C}, fo);
-  CHECK_RC(dpe_gram(bp(x), fpo(coef), scoef, M, (int)C, fp(ws), fp(G), fp(sv), cur_stream()), "bn_gram");
+  CHECK_RC(dpe_gram(bp(x), fpo(coef), scoef, M, (int)C, fp(ws), fp(G), fp(sv), cur_stream(), stride2 ? (int)x.size(1) : 0,
+                    stride2 ? (int)x.size(2) : 0), "bn_gram");
   return {G, sv};
 }
 
@@ -1442,6 +1457,71 @@ std::vector<Tensor> conv1x1_dgrad_cat(const Tensor& dz, const Tensor& a2src, con
   const int rc = dpe_igemm_dma_launch(&a, bm, bn, dpe::A_DENSE_K, dpe::B_DENSE_N, dpe::EPI_BF16_BNB, cur_stream());
   CHECK_RC(rc, "igemm_dma AX_CAT data grad");
   return {dx, part};
+}
+
+// Pilot shift for bn_gram's shift_coef when x has no producing BN (a downsample conv's block input): [4][C] =
+// (1, 0, mean of a fixed sample of x's rows, 0), the degenerate BN description bngram.hip's relu_gauss_mean
+// turns into the (5-bit) mean itself.
+Tensor bn_gram_pilot(const Tensor& x, bool stride2) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x);
+  TORCH_CHECK(!stride2 || (x.dim() == 4 && x.size(1) % 2 == 0 && x.size(2) % 2 == 0), "bn_gram_pilot: stride2 needs [N, H, W, C], even H, W");
+  const int64_t C = x.size(-1), M = x.numel() / C / (stride2 ? 4 : 1);
+  TORCH_CHECK(C == 64 || C == 128 || C == 256, "bn_gram_pilot: C must be 64, 128 or 256");
+  Tensor coef = at::empty({4, C}, x.options().dtype(at::kFloat));
+  CHECK_RC(dpe_gram_pilot(bp(x), M, (int)C, fp(coef), cur_stream(), stride2 ? (int)x.size(1) : 0,
+                          stride2 ? (int)x.size(2) : 0), "bn_gram_pilot");
+  return coef;
+}
+
+// u = W G [Cout][Cin] (fp32) alone: bn_gram_coef's by-product without its BN coefficients / running-statistics
+// update (the downsample BN's were produced by bn_coef in the forward).
+Tensor bn_gram_u(const Tensor& G, const Tensor& w) {
+  CHECK_GPU(G); CHECK_F32(G); CHECK_CONTIG(G); CHECK_BF16(w); CHECK_CONTIG(w);
+  const int64_t Cin = G.size(0), Cout = w.size(0);
+  TORCH_CHECK(G.dim() == 2 && G.size(1) == Cin && w.numel() == Cout * Cin, "bn_gram_u: shapes");
+  Tensor u = at::empty({Cout, Cin}, G.options());
+  CHECK_RC(dpe_gram_u(fp(G), bp(w), (int)Cin, (int)Cout, fp(u), cur_stream()), "bn_gram_u");
+  return u;
+}
+
+// dx = [dz | x] x bcat + e: the concatenated-K data grad of a downsample branch whose BN runs by Gram algebra
+// (x the block input, plain; no BN-backward partials).  Stride 1: streaming kernel (pwconv.hip pw_cat_kernel,
+// BN = false), (K1, C) in {(256, 64), (512, 128)}.  stride2: dz is [N, H/2, W/2, K1], the second segment is the
+// stride-2 subsample of x [N, H, W, C] by row addressing and the result is the compact [N, H/2, W/2, C] grid (the
+// streaming conv1 data grad adds it at the even pixels): the LDS-DMA implicit GEMM's AX_CAT.  bnd_gram_ok below.
+Tensor conv1x1_dgrad_cat_plain(const Tensor& dz, const Tensor& x, const Tensor& bcat, const Tensor& e, bool stride2) {
+  CHECK_GPU(dz); CHECK_BF16(dz); CHECK_CONTIG(dz); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(bcat); CHECK_CONTIG(bcat);
+  CHECK_F32(e);
+  const int64_t K1 = dz.size(-1), M = dz.numel() / K1, C = x.size(-1);
+  if (stride2) {
+    TORCH_CHECK(x.dim() == 4 && dz.dim() == 4 && x.size(1) == 2 * dz.size(1) && x.size(2) == 2 * dz.size(2) &&
+                    x.size(0) == dz.size(0) && bcat.dim() == 2 && bcat.size(0) == K1 + C && bcat.size(1) == C &&
+                    e.numel() == C && K1 % 32 == 0 && C % 32 == 0,
+                "conv1x1_dgrad_cat_plain: stride-2 shapes");
+    Tensor dx = at::empty({dz.size(0), dz.size(1), dz.size(2), C}, x.options());
+    auto a = base_args();
+    a.A = bp(dz); a.B = bp(bcat); a.C = dx.data_ptr();
+    a.M = (int)M; a.N = (int)C; a.K = (int)(K1 + C);
+    a.lda = K1; a.ldb = C; a.ldc = C;
+    a.k_split = a.K;
+    a.bias = fp(e);
+    a.a_mode = dpe::AX_CAT;
+    a.a2 = bp(x); a.lda2 = C; a.k1 = (int)K1;
+    a.a2_h = (int)x.size(1); a.a2_w = (int)x.size(2);
+    CHECK_RC(dpe_igemm_dma_launch(&a, 128, C <= 64 ? 64 : 128, dpe::A_DENSE_K, dpe::B_DENSE_N, dpe::EPI_BF16, cur_stream()),
+             "igemm_dma AX_CAT data grad (stride-2 second segment)");
+    return dx;
+  }
+  TORCH_CHECK(x.numel() == M * C && bcat.dim() == 2 && bcat.size(0) == K1 + C && bcat.size(1) == C && e.numel() == C,
+              "conv1x1_dgrad_cat_plain: shapes");
+  const int rg = dpe_pw_cat_blocks(M, K1, C);
+  TORCH_CHECK(rg > 0, "conv1x1_dgrad_cat_plain: outside the streaming concatenated-K kernel's envelope");
+  Tensor dx = at::empty_like(x);
+  dpe::PwCatArgs pa{};
+  pa.dz = bp(dz); pa.h2 = bp(x); pa.bcat = bp(bcat); pa.ebias = fp(e);
+  pa.y = bpm(dx); pa.M = M; pa.rg = rg;
+  CHECK_RC(dpe_pw_cat_launch(&pa, K1, C, cur_stream()), "pw_cat data grad (plain)");
+  return dx;
 }
 
 // BatchNorm coefficients [4][C] (scale, shift, mean, invstd) from conv-epilogue
@@ -2200,6 +2280,7 @@ void register_ops(pybind11::module& m) {
         "data grad; with bn_x/bn_coef also the BN-backward partials of the BN+ReLU that produced the conv input; "
         "with bn_mask (BN + residual + ReLU) the mask is bn_mask > 0 and dx is stored masked");
   m.def("bn_gram", &bn_gram, py::arg("x"), py::arg("coef") = py::none(), py::arg("shift_coef") = py::none(),
+        py::arg("stride2") = false,
         "(G = a'^T a', s = [colsum(a'), mu]) of a' = a2 - mu, a2 = relu(x * coef[0] + coef[1]) (or x), centred on the "
         "pilot shift of shift_coef (default coef); fp32, deterministic");
   m.def("bn_gram_coef", &bn_gram_coef, py::arg("G"), py::arg("s"), py::arg("w"), py::arg("M"), py::arg("gamma"),
@@ -2214,6 +2295,30 @@ void register_ops(pybind11::module& m) {
   m.def("conv1x1_dgrad_cat", &conv1x1_dgrad_cat, py::arg("dz"), py::arg("a2src"), py::arg("a2_coef"), py::arg("bcat"),
         py::arg("e"), py::arg("bn_x"), py::arg("bn_coef"),
         "[dz | a2] x bcat + e with the BN2-backward partials (concatenated-K data grad)");
+  m.def("bn_gram_pilot", &bn_gram_pilot, py::arg("x"), py::arg("stride2") = false,
+        "pilot shift [4][C] for bn_gram's shift_coef from a sample of x's rows (x without a producing BN)");
+  m.def("bn_gram_u", &bn_gram_u, py::arg("G"), py::arg("w"), "u = W G (fp32) alone: no coefficients, no running stats");
+  m.def("conv1x1_dgrad_cat_plain", &conv1x1_dgrad_cat_plain, py::arg("dz"), py::arg("x"), py::arg("bcat"), py::arg("e"),
+        py::arg("stride2") = false,
+        "[dz | x] x bcat + e (concatenated-K data grad of a Gram-path downsample branch, no partials)");
+  m.def("bnd_gram_ok", [](std::vector<int64_t> xshape, int64_t cout, std::vector<int64_t> stride) {
+          // the downsample BN by Gram algebra for a 1x1 stride-1 downsample conv over x [N, H, W, Cin]: the Gram
+          // pass over x, the deterministic LDS-DMA weight grad P_d = dz3^T x, and the streaming concatenated-K
+          // data grad (Cin -> 4 Cin, Cin in {64, 128})
+          // stride 2 (layer2.0: 256 -> 512 over the even pixels): the Gram pass and the data grad's second segment
+          // address the subsample of x by rows (LDS-DMA kernels), and P_d runs on the persistent GEMM's
+          // implicit-im2col weight grad (fixed-order slabs), whose envelope is tested here
+          if (xshape.size() != 4 || stride.size() != 2 || stride[0] != stride[1] || !igemm_dma_on()) return false;
+          const int64_t M = xshape[0] * xshape[1] * xshape[2], C = xshape[3];
+          // (stride 1: P_d's LDS-DMA weight grad needs Cout, C % 8 and M Cout 2 B < 2^31 -- the channel test and
+          // dpe_pw_cat_blocks' own size limit imply both)
+          if (stride[0] == 1) return (C == 64 || C == 128) && cout == 4 * C && dpe_pw_cat_blocks(M, cout, C) > 0;
+          if (stride[0] != 2 || xshape[1] % 2 || xshape[2] % 2) return false;
+          static const bool gdma = [] { const char* e = getenv("DPE_GRAM_DMA"); return !(e && e[0] == '0'); }();
+          const int64_t Mo = M / 4, lim = (1ll << 31) - 4096;
+          return gdma && (C == 64 || C == 128 || C == 256) && cout >= 256 && cout % 32 == 0 && g_hgemm_conv &&
+                 g_hgemm_conv_wgrad && Mo % 64 == 0 && Mo < (1 << 24) && M * C * 2 < lim && Mo * cout * 2 < lim;
+        }, py::arg("xshape"), py::arg("cout"), py::arg("stride"));
   m.def("bn_bwd_coef", &bn_bwd_coef, py::arg("partials"), py::arg("M"), py::arg("gamma"), py::arg("coef"),
         py::arg("dgamma") = py::none(), py::arg("dbeta") = py::none(),
         "BN-backward coefficients [3][C] from the dgrad-epilogue partials (no apply pass); dgamma/dbeta +=");
@@ -2246,7 +2351,8 @@ void register_ops(pybind11::module& m) {
         py::arg("dil"), py::arg("alpha") = 1.0, py::arg("in_coef") = py::none(), py::arg("fin_stream") = 0,
         py::arg("deterministic") = false, py::arg("overwrite") = false,
         "dw (+)= alpha dW; fin_stream: a K-split hgemm's slab reduction runs on that stream (caller orders consumers); "
-        "deterministic: 1x1 weight grads over a pre-BN input sum their K splits in a fixed order (no atomics); "
+        "deterministic: 1x1 weight grads on the LDS-DMA kernel (pre-BN or plain input, < 256 channels on a side) and the "
+        "persistent GEMM's sum their K splits in a fixed order (no atomics); "
         "overwrite: dw = alpha dW (dw's old contents, e.g. torch.empty, are never read)");
   m.def("bn_fwd_train", &bn_fwd_train, py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("rmean"), py::arg("rvar"),
         py::arg("momentum"), py::arg("eps"), py::arg("relu"), py::arg("residual") = py::none(), py::arg("stats") = py::none());

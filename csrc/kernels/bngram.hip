@@ -284,11 +284,22 @@ DPE_DEVICE void gram_sfor(F&& f) {
   gram_sfor_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-template <int C>
+// Row m of the stride-2 subsample of an [*, sh, sw] image -> its pixel index (n, 2 oh, 2 ow) in the full image
+DPE_DEVICE int64_t gram_s2_pixel(int64_t m, int sh, int sw) {
+  const int ow_ = sw >> 1, per = (sh >> 1) * ow_;
+  const int64_t n = m / per;
+  const int r = (int)(m - n * per), oh = r / ow_, ow = r - oh * ow_;
+  return (n * sh + 2 * oh) * sw + 2 * ow;
+}
+
+// STR: the M rows are the stride-2 subsample x[:, ::2, ::2, :] of an [*, sh, sw, C] image (a stride-2 1x1 conv's
+// input pixels), taken by row addressing -- every DMA piece's rows are mapped to their pixel offsets per group
+// (whole 2 C-byte pixel rows), no compacting copy.
+template <int C, bool STR = false>
 __global__ __launch_bounds__(512, 1) void gram_dma_kernel(const uint16_t* __restrict__ x, const float* __restrict__ coef,
                                                           const float* __restrict__ scoef, int64_t M, int rpb,
                                                           float* __restrict__ gp, float* __restrict__ sp,
-                                                          float* __restrict__ mu_out) {
+                                                          float* __restrict__ mu_out, int sh, int sw) {
   constexpr int NT = 512, NW = 8;
   constexpr int CPR = C / 8, RB = 2 * C, SB = TR * RB;  // chunks per row, bytes per row / tile
   constexpr int NS = C == 256 ? 8 : (C == 128 ? 12 : 16); // ring depth (tiles)
@@ -313,21 +324,32 @@ __global__ __launch_bounds__(512, 1) void gram_dma_kernel(const uint16_t* __rest
   }
   // DMA: lane l of the group's piece q (= wid + NW v) fills byte 1024 q + 16 l of the group's GT tiles
   const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(x), (short)0, (int)(M * C * 2), 0x00020000);
-  uint32_t voff[DPG];
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(x), (short)0, (int)((STR ? 4 : 1) * M * C * 2), 0x00020000);
+  uint32_t voff[DPG];  // (STR: the chunk's byte offset inside its pixel row; lrow = its row within the group)
+  int lrow[DPG];
 #pragma unroll
   for (int v = 0; v < DPG; ++v) {
     const int o = ((wid + NW * v) * 1024 + lane * 16) % SB, tk = ((wid + NW * v) * 1024) / SB;
     const int row = o / RB, chs = (o % RB) / 16;
     const int ch = chs ^ (2 * gram_h(row, C));
-    voff[v] = (uint32_t)(((tk * TR + row) * C + ch * 8) * 2);
+    lrow[v] = tk * TR + row;
+    voff[v] = STR ? (uint32_t)(ch * 16) : (uint32_t)(((tk * TR + row) * C + ch * 8) * 2);
   }
   const int ngrp = (ntile + GT - 1) / GT;
   // group q = tiles [q GT, q GT + GT) in ring slots (q % NG) GT + [0, GT); rows past the block's range (the
   // next block's, or zeros past M) are masked in the transform
   auto dma_group = [&](int q) {
-    const uint32_t so = (uint32_t)((r0 + (int64_t)q * GT * TR) * C * 2);
     char* slot = ring + (q % NG) * GT * SB;
+    if constexpr (STR) {
+      // (rows past M are clamped to the last row: in range, masked in the transform)
+#pragma unroll
+      for (int v = 0; v < DPG; ++v) {
+        const int64_t m = min<int64_t>(r0 + (int64_t)q * GT * TR + lrow[v], M - 1);
+        gram_dma16(rs, slot + (wid + NW * v) * 1024, (uint32_t)(gram_s2_pixel(m, sh, sw) * (C * 2)) + voff[v], 0u);
+      }
+      return;
+    }
+    const uint32_t so = (uint32_t)((r0 + (int64_t)q * GT * TR) * C * 2);
 #pragma unroll
     for (int v = 0; v < DPG; ++v) gram_dma16(rs, slot + (wid + NW * v) * 1024, voff[v], so);
   };
@@ -441,6 +463,43 @@ __global__ __launch_bounds__(512, 1) void gram_dma_kernel(const uint16_t* __rest
     for (int e = 0; e < 4; ++e) Gt[(int64_t)fl * 256 + e * 64 + lane] = acc[i][e];
     const int f = gram_frag(fl, NB, NF);
     if ((f >> 8) == (f & 255) && g == 0) sp[(int64_t)blockIdx.x * C + 16 * (f & 255) + li] = csa[i][0];
+  }
+}
+
+// Pilot shift of a plain operand (no producing BN whose coefficients relu_gauss_mean could work from: the
+// block input x of a downsample conv): the per-channel mean of ns rows spread evenly over the M rows, written
+// as the degenerate BN description [4][C] = (scale 1, shift 0, mean, invstd 0) -- sigma = 0, for which
+// relu_gauss_mean returns max(mean, 0) rounded to its 5 significant bits.  Any mu within O(std) of the column
+// mean removes the cancellation; a few hundred rows put the sample mean within a small fraction of one std.
+// One block; the partial sums of a channel chunk are added in a fixed order (deterministic).
+// (sh > 0: the M rows are the stride-2 subsample of an [*, sh, sw, C] image, as gram_dma_kernel's STR)
+__global__ __launch_bounds__(256) void gram_pilot_kernel(const uint16_t* __restrict__ x, int64_t M, int C, int ns,
+                                                         float* __restrict__ coef, int sh, int sw) {
+  __shared__ float red[256][9];
+  const int tid = threadIdx.x, cpr = C / 8, nr = 256 / cpr;  // C <= 256: nr >= 8 sample-row groups
+  const int tc = tid % cpr, tr = tid / cpr;
+  float a[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) a[e] = 0.f;
+#pragma unroll 4
+  for (int i = tr; i < ns; i += nr) {
+    int64_t row = (int64_t)i * M / ns;  // ns <= M: distinct rows < M
+    if (sh > 0) row = gram_s2_pixel(row, sh, sw);
+    float f[8];
+    unpack8(*(const u32x4*)(x + row * C + 8 * tc), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] += f[e];
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) red[tid][e] = a[e];
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float t = 0.f;
+    for (int r = 0; r < nr; ++r) t += red[r * cpr + (c >> 3)][c & 7];
+    coef[c] = 1.f;
+    coef[C + c] = 0.f;
+    coef[2 * C + c] = t / (float)ns;
+    coef[3 * C + c] = 0.f;
   }
 }
 
@@ -833,9 +892,12 @@ extern "C" int dpe_gram_blocks(int64_t M, int C) {
 }
 extern "C" int64_t dpe_gram_ws_floats(int64_t M, int C) { return (int64_t)dpe_gram_blocks(M, C) * ((int64_t)C * C + C); }
 
+// sh, sw > 0: x is an [*, sh, sw, C] image and the M rows are its stride-2 subsample (LDS-DMA kernel only)
 extern "C" int dpe_gram(const uint16_t* x, const float* coef, const float* scoef, int64_t M, int C, float* ws, float* G,
-                        float* s, hipStream_t st) {
+                        float* s, hipStream_t st, int sh, int sw) {
   if (C != 64 && C != 128 && C != 256) return -1;
+  const bool str = sh > 0;
+  if (str && (sh % 2 || sw % 2 || sw <= 0 || M % ((int64_t)(sh / 2) * (sw / 2)))) return -1;
   const int nb = dpe_gram_blocks(M, C);
   const int64_t tiles = (M + gram::TR - 1) / gram::TR;
   const int rpb = (int)(((tiles + nb - 1) / nb) * gram::TR);
@@ -844,14 +906,22 @@ extern "C" int dpe_gram(const uint16_t* x, const float* coef, const float* scoef
   float* mu = s + C;
   // DPE_GRAM_DMA=0: the register-staged kernel (A/B)
   const bool dma = gram_dma_on();
-  const bool dma_used = dma && M * C * 2 < (1ll << 31) - 4096;
-  if (dma_used) {
+  const bool dma_used = dma && (str ? 4 : 1) * M * C * 2 < (1ll << 31) - 4096;
+  if (str && !dma_used) return -1;
+  if (str) {
     if (C == 64)
-      hipLaunchKernelGGL(gram::gram_dma_kernel<64>, dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu);
+      hipLaunchKernelGGL((gram::gram_dma_kernel<64, true>), dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu, sh, sw);
     else if (C == 128)
-      hipLaunchKernelGGL(gram::gram_dma_kernel<128>, dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu);
+      hipLaunchKernelGGL((gram::gram_dma_kernel<128, true>), dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu, sh, sw);
     else
-      hipLaunchKernelGGL(gram::gram_dma_kernel<256>, dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu);
+      hipLaunchKernelGGL((gram::gram_dma_kernel<256, true>), dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu, sh, sw);
+  } else if (dma_used) {
+    if (C == 64)
+      hipLaunchKernelGGL(gram::gram_dma_kernel<64>, dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu, 0, 0);
+    else if (C == 128)
+      hipLaunchKernelGGL(gram::gram_dma_kernel<128>, dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu, 0, 0);
+    else
+      hipLaunchKernelGGL(gram::gram_dma_kernel<256>, dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu, 0, 0);
   } else if (C == 64)
     hipLaunchKernelGGL(gram::gram_partial_kernel<64>, dim3(nb), dim3(256), 0, st, x, coef, scoef, M, rpb, gp, sp, mu);
   else if (C == 128)
@@ -859,7 +929,7 @@ extern "C" int dpe_gram(const uint16_t* x, const float* coef, const float* scoef
   else
     hipLaunchKernelGGL(gram::gram_partial_kernel<256>, dim3(nb), dim3(512), 0, st, x, coef, scoef, M, rpb, gp, sp, mu);
   const int64_t n = (int64_t)C * C + C;
-  if (dma_used) {
+  if (dma_used || str) {
     const int64_t nf = (int64_t)(C / 16) * (C / 16 + 1) / 2, nt = nf * 256 + C;
     hipLaunchKernelGGL(gram::gram_reduce_tri_kernel, dim3((unsigned)((nt + 31) / 32)), dim3(256), 0, st, gp, sp, nb, C, G, s);
   }
@@ -868,14 +938,28 @@ extern "C" int dpe_gram(const uint16_t* x, const float* coef, const float* scoef
   return 0;
 }
 
-extern "C" int dpe_gram_coef(const float* G, const float* s, const uint16_t* w, int Cin, int Cout, int64_t M,
-                             const float* gamma, const float* beta, float* rmean, float* rvar, float momentum, float eps,
-                             float* coef, float* u, hipStream_t st) {
+// Pilot shift for dpe_gram's scoef from a sample of x's rows (x has no producing BN): coef [4][C]
+extern "C" int dpe_gram_pilot(const uint16_t* x, int64_t M, int C, float* coef, hipStream_t st, int sh, int sw) {
+  if ((C != 64 && C != 128 && C != 256) || M <= 0) return -1;
+  if (sh > 0 && (sh % 2 || sw % 2 || sw <= 0 || M % ((int64_t)(sh / 2) * (sw / 2)))) return -1;
+  const int ns = (int)std::min<int64_t>(M, 512);
+  hipLaunchKernelGGL(gram::gram_pilot_kernel, dim3(1), dim3(256), 0, st, x, M, C, ns, coef, sh, sw);
+  return 0;
+}
+
+// u = W G  (M = Cout, N = Cin, K = Cin) alone: no BN coefficients, no running statistics touched
+extern "C" int dpe_gram_u(const float* G, const uint16_t* w, int Cin, int Cout, float* u, hipStream_t st) {
   if (Cin % 32 || Cout % 32 || Cin > 256) return -1;
-  // u = W G  (M = Cout, N = Cin, K = Cin)
   hipLaunchKernelGGL((gram::gram_mm_kernel<false, float, 256>), dim3(Cin / 32, Cout / 32, 1), dim3(256), 0, st, w,
                      (int64_t)Cin, (const float*)nullptr, G, (int64_t)Cin, Cin, Cin, u, (int64_t)Cin, (int64_t)0,
                      (const float*)nullptr, (float*)nullptr);
+  return 0;
+}
+
+extern "C" int dpe_gram_coef(const float* G, const float* s, const uint16_t* w, int Cin, int Cout, int64_t M,
+                             const float* gamma, const float* beta, float* rmean, float* rvar, float momentum, float eps,
+                             float* coef, float* u, hipStream_t st) {
+  if (dpe_gram_u(G, w, Cin, Cout, u, st) != 0) return -1;
   hipLaunchKernelGGL(gram::gram_coef_kernel, dim3((Cout + 3) / 4), dim3(256), 0, st, u, s, w, Cin, Cout, M, gamma, beta,
                      rmean, rvar, momentum, eps, coef);
   return 0;

@@ -93,6 +93,8 @@ struct IgemmArgs {
   uint8_t* a_bits;          // [M][lda/8] ReLU-mask bits of a_out (AX_BN_RES / _RES2), or nullptr
   int k1;                   // AX_CAT: K of the first segment (multiple of 32)
   int64_t lda2;             // AX_CAT: row stride of a2
+  int a2_h, a2_w;           // AX_CAT, > 0: a2 is an [*, a2_h, a2_w, lda2] image and row m of the second segment is
+                            //   pixel m of its stride-2 subsample [*, a2_h/2, a2_w/2] (0: dense rows)
   float* slab;              // LDS-DMA weight grad only: EPI_ATOMIC_F32 partials STORED to slab[split][M][N]
                             //   (summed in split order by a finalize pass: deterministic) instead of atomics
 };

@@ -830,8 +830,9 @@ DPE_DEVICE void igemm_dma_body(const IgemmArgs& p, int a_dense, const int bid) {
   const int64_t abytes = a_dense ? (int64_t)p.M * p.lda * 2 : ((int64_t)g.N * g.H * g.W * g.C + apre) * 2;
   const __amdgpu_buffer_rsrc_t ar = dma_rsrc(p.A - apre, (uint32_t)abytes);
   const __amdgpu_buffer_rsrc_t ar2 =
-      CAT ? dma_rsrc(p.a2, (uint32_t)((int64_t)p.M * p.lda2 * 2)) : dma_rsrc(AX ? p.a2 : p.A, (uint32_t)abytes);
-  // AX_CAT: the second segment's per-piece row offsets (dense rows, lda2)
+      CAT ? dma_rsrc(p.a2, (uint32_t)((p.a2_h > 0 ? 4 : 1) * (int64_t)p.M * p.lda2 * 2))
+          : dma_rsrc(AX ? p.a2 : p.A, (uint32_t)abytes);
+  // AX_CAT: the second segment's per-piece row offsets (dense rows, lda2; or the pixels of a stride-2 subsample)
   uint32_t aoff2[CAT ? PA : 1];
   if constexpr (CAT) {
 #pragma unroll
@@ -839,7 +840,13 @@ DPE_DEVICE void igemm_dma_body(const IgemmArgs& p, int a_dense, const int bid) {
       const int row = (wid * PA + i) * 16 + (lane >> 2);
       const int lc = (lane & 3) ^ ((0x78 >> (((row >> 2) & 3) << 1)) & 3);
       const int m = m0 + row;
-      aoff2[i] = m < p.M ? (uint32_t)m * (uint32_t)p.lda2 * 2u + lc * 16 : DMA_OOB;
+      int64_t pix = m;
+      if (p.a2_h > 0 && m < p.M) {
+        const int ow_ = p.a2_w >> 1, per = (p.a2_h >> 1) * ow_;
+        const int n = m / per, r = m - n * per, oh = r / ow_, ow = r - oh * ow_;
+        pix = ((int64_t)n * p.a2_h + 2 * oh) * p.a2_w + 2 * ow;
+      }
+      aoff2[i] = m < p.M ? (uint32_t)pix * (uint32_t)p.lda2 * 2u + lc * 16 : DMA_OOB;
     }
   }
 
@@ -1111,7 +1118,7 @@ DPE_DEVICE int mn_swz(int k) {
 // (profiles/wgrad_bigtile_ab_r2.txt): at ~210 VGPRs they run 2 waves per SIMD where 128x128
 // runs 4, and the one-barrier-per-32-K ring does not hide the DMA latency at that occupancy.
 // Not instantiated; the waves-per-EU bound below is what such a tile needs.
-template <int BM, int BN, int BL, int WGM = 2, int WGN = 2, int NS = DSTAGES>
+template <int BM, int BN, int BL, int WGM = 2, int WGN = 2, int NS = DSTAGES, bool KTAIL = false>
 // (the 4-wave tiles need <= 128 VGPRs for 4 waves per SIMD: a build of the 128x128 3x3 tile at 133 ran 1.3x
 // slower; check scripts/isa_stats.py after edits -- a launch bound forcing it spilled the 1x1 tile instead)
 __global__ __launch_bounds__(64 * WGM * WGN, (BN / WGN > 64) ? 2 : 1) void igemm_wgrad_dma_kernel(IgemmArgs p) {
@@ -1137,7 +1144,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BN / WGN > 64) ? 2 : 1) void igemm
   const int m0 = (tile / tilesN) * BM, n0 = (tile % tilesN) * BN;
   const int kb = split * p.k_split;
   const int ke = min(p.K, kb + p.k_split);
-  const int nt = (ke - kb) / BK;
+  // KTAIL (dense B only): K % 32 != 0, the last step's rows past K are fetched at the out-of-range offset and
+  // land as zeros (with b_coef the B rows become relu(shift), times A's zeros)
+  static_assert(!KTAIL || BL == B_DENSE_N, "K tail: dense B only");
+  const int nt = KTAIL ? (ke - kb + BK - 1) / BK : (ke - kb) / BK;
   const int wm = (wid / WGN) * (BM / WGM), wn = (wid % WGN) * (BN / WGN);
   const ConvGeom& g = p.g;
 
@@ -1198,7 +1208,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BN / WGN > 64) ? 2 : 1) void igemm
   auto issue = [&](int buf) {
     char* st = smem + buf * STAGE;
 #pragma unroll
-    for (int i = 0; i < PA; ++i) dma16(ar, st + (wid * PA + i) * 1024, aoff[i], kso * astep);
+    for (int i = 0; i < PA; ++i) {
+      uint32_t vo = aoff[i];
+      if constexpr (KTAIL)
+        if (kb + (int)kso * BK + (wid * PA + i) * AKR + lane / ACPR >= p.K) vo = DMA_OOB;
+      dma16(ar, st + (wid * PA + i) * 1024, vo, kso * astep);
+    }
 #pragma unroll
     for (int i = 0; i < PB; ++i) {
       if constexpr (CONV) {
@@ -1209,7 +1224,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BN / WGN > 64) ? 2 : 1) void igemm
         if (ow[i] >= g.OW) { ow[i] -= g.OW; oh[i] += 1; roff[i] += d_ow; }
         if (oh[i] >= g.OH) { oh[i] -= g.OH; roff[i] += d_oh; }
       } else {
-        dma16(br, st + A_BYTES + (wid * PB + i) * 1024, boff[i], kso * bstep);
+        uint32_t vo = boff[i];
+        if constexpr (KTAIL)
+          if (kb + (int)kso * BK + (wid * PB + i) * BKR + lane / BCPR >= p.K) vo = DMA_OOB;
+        dma16(br, st + A_BYTES + (wid * PB + i) * 1024, vo, kso * bstep);
       }
     }
     ++kso;
@@ -1345,7 +1363,10 @@ extern "C" int dpe_igemm_dma_launch(const IgemmArgs* args, int bm, int bn, int a
   if (a.a_mode == AX_CAT) {
     // concatenated-K data grad: A segments dense, K1 = k1 from A (lda), K - k1 from a2 (lda2)
     if (!dense || !a.a2 || a.k1 <= 0 || a.k1 % 32 || a.k1 >= a.K || a.lda < a.k1 || a.lda2 < a.K - a.k1 ||
-        a.lda2 % 8 || (int64_t)a.M * a.lda2 * 2 >= lim || a.K - a.k1 > 2048)
+        a.lda2 % 8 || (a.a2_h > 0 ? 4 : 1) * (int64_t)a.M * a.lda2 * 2 >= lim || a.K - a.k1 > 2048)
+      return -1;
+    if (a.a2_h < 0 || (a.a2_h > 0 && (a.a2_h % 2 || a.a2_w % 2 || a.a2_w <= 0 ||
+                                      a.M % ((a.a2_h / 2) * (a.a2_w / 2)))))
       return -1;
 #define DPE_DMA_CAT(BM_, BN_, WGM_, WGN_, BL_, EP_)                                                         \
   if (bm == BM_ && bn == BN_ && bload == BL_ && epi == EP_) {                                               \
@@ -1467,7 +1488,9 @@ extern "C" int dpe_igemm_wgrad_dma_launch(const IgemmArgs* args, int bm, int bn,
   const IgemmArgs& a = *args;
   if (a.M <= 0 || a.N <= 0) return 0;
   if (bload != B_DENSE_N && bload != B_CONV_WGRAD) return -1;
-  if (a.K <= 0 || a.K % 32 || a.k_split % 32 || a.M % 8 || a.N % 8 || a.lda % 8 || a.ldb % 8) return -1;
+  // (K % 32: the im2col pixel walk advances whole 32-pixel steps; the dense B has a tail-step instantiation)
+  if (a.K <= 0 || (a.K % 32 && bload != B_DENSE_N) || a.k_split % 32 || a.M % 8 || a.N % 8 || a.lda % 8 || a.ldb % 8)
+    return -1;
   const int64_t lim = (1ll << 31) - 4096;
   if ((int64_t)a.K * a.lda * 2 >= lim) return -1;
   const ConvGeom& g = a.g;
@@ -1485,6 +1508,14 @@ extern "C" int dpe_igemm_wgrad_dma_launch(const IgemmArgs* args, int bm, int bn,
     hipLaunchKernelGGL((igemm_wgrad_dma_kernel<BM_, BN_, BL_, 2, 2, DPE_WG_NS>), dim3(tiles * splits), dim3(NT), 0, st, a); \
     return 0;                                                                                                 \
   }
+#define DPE_WG_TAIL(BM_, BN_)                                                                                  \
+  if (bm == BM_ && bn == BN_ && bload == B_DENSE_N && a.K % 32) {                                             \
+    hipLaunchKernelGGL((igemm_wgrad_dma_kernel<BM_, BN_, B_DENSE_N, 2, 2, DPE_WG_NS, true>), dim3(tiles * splits), \
+                       dim3(NT), 0, st, a);                                                                   \
+    return 0;                                                                                                 \
+  }
+  DPE_WG_TAIL(128, 128) DPE_WG_TAIL(128, 64) DPE_WG_TAIL(64, 128) DPE_WG_TAIL(64, 64)
+#undef DPE_WG_TAIL
 #define DPE_WG_T(BL_) DPE_WG(128, 128, BL_) DPE_WG(128, 64, BL_) DPE_WG(64, 128, BL_) DPE_WG(64, 64, BL_)
   DPE_WG_T(B_DENSE_N)
   DPE_WG_T(B_CONV_WGRAD)

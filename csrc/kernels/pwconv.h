@@ -39,14 +39,16 @@ struct PwArgs {
 //   y[M][N] = [dz | relu(h2 * s + t)] . Bcat + e,  N = K2 (the bottleneck width: 64 or 128), K1 = 4 N,
 // with the BN2-backward partials (sum dz, sum dz*(h2 - mean)) of the stored y; mask and h2 from the raw h2
 // tile the kernel already holds in LDS (the LDS-DMA implicit GEMM re-read h2 for its epilogue).
+// coef == nullptr (and stats == nullptr): the second segment is a plain operand, y = [dz | h2] . Bcat + e with no
+// partials (the downsample BN's Gram backward: h2 = the block input x).
 struct PwCatArgs {
   const uint16_t* dz;     // [M][K1] bf16
-  const uint16_t* h2;     // [M][K2] bf16, pre-BN2
-  const float* coef;      // BN2 [4][K2]: scale, shift, mean, invstd
+  const uint16_t* h2;     // [M][K2] bf16, pre-BN2 (or the plain operand)
+  const float* coef;      // BN2 [4][K2]: scale, shift, mean, invstd, or nullptr
   const uint16_t* bcat;   // [K1 + K2][N] bf16
   const float* ebias;     // [N]
   uint16_t* y;            // [M][N] bf16
-  float* stats;           // [2][N][rg]
+  float* stats;           // [2][N][rg], or nullptr (with coef == nullptr)
   int64_t M;
   int rg;                 // blocks (= partial columns)
 };

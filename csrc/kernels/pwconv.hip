@@ -513,8 +513,10 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
 // cooperatively, into a separate a2 image (relu(h2 s + t), rounded to bf16 as every on-load BN here); the
 // MFMAs read dz / a2 fragments; the epilogue adds e, rounds, and takes the BN2 mask and h2 - mean from the
 // RAW h2 images still in the ring slot -- no second HBM read of h2.  One partial column per block.
+// BN = false: the second segment is a plain operand (the block input x of a downsample conv, BN_d's Gram
+// backward): y = [dz | x] . Bcat + e, no on-load transform (the MFMAs read the raw images), no partials.
 constexpr int CBM = 32;
-template <int K1, int K2, int NS>
+template <int K1, int K2, int NS, bool BN = true>
 __global__ __launch_bounds__(64 * (K2 / 16), K2 == 64 ? 2 : 1) void pw_cat_kernel(PwCatArgs a) {
   constexpr int NW = K2 / 16, NT = 64 * NW, N = K2;
   constexpr int KC1 = K1 / 32, KC2 = K2 / 32, KC = KC1 + KC2;
@@ -528,15 +530,16 @@ __global__ __launch_bounds__(64 * (K2 / 16), K2 == 64 ? 2 : 1) void pw_cat_kerne
   constexpr int VM = (NS - 1) * S + (NS - 2) * P;
   static_assert(VM < 64, "vmcnt range");
   // one LDS object (see pw_stream_kernel): ring, a2 image, staging, BN2's [scale | shift]
-  __shared__ __attribute__((aligned(16))) char smem[NS * TILE + KC2 * IMG + NW * STG + 2 * K2 * 4];
-  float* const bnin = (float*)(smem + NS * TILE + KC2 * IMG + NW * STG);
+  constexpr int A2B = BN ? KC2 * IMG : 0, BNB = BN ? 2 * K2 * 4 : 16;  // (the plain form has no a2 image / BN table)
+  __shared__ __attribute__((aligned(16))) char smem[NS * TILE + A2B + NW * STG + BNB];
+  float* const bnin = (float*)(smem + NS * TILE + A2B + NW * STG);
   char* const a2img = smem + NS * TILE;
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, li = lane & 15;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int M = (int)a.M, RG = a.rg;
   const int tiles = (M + CBM - 1) / CBM;
   const int n0w = wid * 16;
-  char* const stg = smem + NS * TILE + KC2 * IMG + wid * STG;
+  char* const stg = smem + NS * TILE + A2B + wid * STG;
   auto swz = [](int row) { return (0x78 >> (((row >> 2) & 3) << 1)) & 3; };
 
   // Bcat columns of the wave's 16 channels: wf[kc] = A rows n0w + li, K = 32 kc + 8 g .. +7
@@ -553,13 +556,15 @@ __global__ __launch_bounds__(64 * (K2 / 16), K2 == 64 ? 2 : 1) void pw_cat_kerne
   float eb[4], bsc[8], bsh[8], bmu[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) eb[e] = a.ebias[n0w + 4 * g + e];
+  if constexpr (BN) {
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    bsc[e] = a.coef[nch + e];
-    bsh[e] = a.coef[K2 + nch + e];
-    bmu[e] = a.coef[2 * K2 + nch + e];
+    for (int e = 0; e < 8; ++e) {
+      bsc[e] = a.coef[nch + e];
+      bsh[e] = a.coef[K2 + nch + e];
+      bmu[e] = a.coef[2 * K2 + nch + e];
+    }
+    for (int i = tid; i < 2 * K2; i += NT) bnin[i] = a.coef[i];
   }
-  for (int i = tid; i < 2 * K2; i += NT) bnin[i] = a.coef[i];
 
   // DMA: piece q (of 2 KC per tile) = image q >> 1, rows 16 (q & 1) .. +15; lane -> (row, 16-B chunk)
   const __amdgpu_buffer_rsrc_t r1 = rsrc(a.dz, (uint32_t)((int64_t)M * K1 * 2));
@@ -614,6 +619,7 @@ __global__ __launch_bounds__(64 * (K2 / 16), K2 == 64 ? 2 : 1) void pw_cat_kerne
     if (j + NS - 1 < nt) issue(rgb + (j + NS - 1) * RG, (j + NS - 1) % NS);
     const char* img = smem + slot * TILE;
     // raw h2 images -> a2 image (same physical positions), once per tile
+    if constexpr (BN) {
 #pragma unroll
     for (int c = tid; c < KC2 * CBM * 4; c += NT) {
       const int kc2 = c / (CBM * 4), rem = c % (CBM * 4), row = rem >> 2, pc = rem & 3;
@@ -631,10 +637,11 @@ __global__ __launch_bounds__(64 * (K2 / 16), K2 == 64 ? 2 : 1) void pw_cat_kerne
       *(u32x4*)(a2img + off) = pack8(f);
     }
     lds_barrier();
+    }
     f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
-      const char* im = kc < KC1 ? img + kc * IMG : a2img + (kc - KC1) * IMG;
+      const char* im = (!BN || kc < KC1) ? img + kc * IMG : a2img + (kc - KC1) * IMG;
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi) acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kc], kfrag(im, 16 * mi), acc[mi], 0, 0, 0);
     }
@@ -649,19 +656,22 @@ __global__ __launch_bounds__(64 * (K2 / 16), K2 == 64 ? 2 : 1) void pw_cat_kerne
     const u32x4 v = *(const u32x4*)(stg + erow * ROWB + (lane & 1) * 16);
     const int m = m0 + erow;
     if (m < M) {
-      float f[8], x8[8];
-      unpack8(v, f);
-      const int kc2 = nch >> 5, lc = (nch & 31) >> 3;
-      unpack8(*(const u32x4*)(img + (KC1 + kc2) * IMG + erow * 64 + ((lc ^ swz(erow)) << 4)), x8);
+      if constexpr (BN) {
+        float f[8], x8[8];
+        unpack8(v, f);
+        const int kc2 = nch >> 5, lc = (nch & 31) >> 3;
+        unpack8(*(const u32x4*)(img + (KC1 + kc2) * IMG + erow * 64 + ((lc ^ swz(erow)) << 4)), x8);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float dz = fmaf(x8[e], bsc[e], bsh[e]) > 0.f ? f[e] : 0.f;
-        s[e] += dz;
-        ss[e] = fmaf(dz, x8[e] - bmu[e], ss[e]);
+        for (int e = 0; e < 8; ++e) {
+          const float dz = fmaf(x8[e], bsc[e], bsh[e]) > 0.f ? f[e] : 0.f;
+          s[e] += dz;
+          ss[e] = fmaf(dz, x8[e] - bmu[e], ss[e]);
+        }
       }
       *(u32x4*)(a.y + (int64_t)m * N + nch) = v;
     }
   }
+  if constexpr (!BN) return;
   // one partial column per block: reduce over the lanes holding the same chunk (lane & 1)
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
@@ -707,9 +717,17 @@ extern "C" int dpe_pw_cat_blocks(int64_t M, int64_t K1, int64_t K2) {
 extern "C" int dpe_pw_cat_launch(const PwCatArgs* args, int64_t K1, int64_t K2, hipStream_t st) {
   const PwCatArgs& a = *args;
   if (a.rg <= 0 || a.rg != dpe_pw_cat_blocks(a.M, K1, K2)) return -1;
-  if (K1 == 256 && K2 == 64) hipLaunchKernelGGL((pw::pw_cat_kernel<256, 64, 3>), dim3(a.rg), dim3(256), 0, st, a);
-  else if (K1 == 512 && K2 == 128) hipLaunchKernelGGL((pw::pw_cat_kernel<512, 128, 3>), dim3(a.rg), dim3(512), 0, st, a);
-  else return -1;
+  const bool bn = a.coef != nullptr;  // (no coefficients: the plain second segment, no partials)
+  if (bn != (a.stats != nullptr)) return -1;
+  if (K1 == 256 && K2 == 64) {
+    if (bn) hipLaunchKernelGGL((pw::pw_cat_kernel<256, 64, 3>), dim3(a.rg), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((pw::pw_cat_kernel<256, 64, 3, false>), dim3(a.rg), dim3(256), 0, st, a);
+  } else if (K1 == 512 && K2 == 128) {
+    if (bn) hipLaunchKernelGGL((pw::pw_cat_kernel<512, 128, 3>), dim3(a.rg), dim3(512), 0, st, a);
+    else hipLaunchKernelGGL((pw::pw_cat_kernel<512, 128, 3, false>), dim3(a.rg), dim3(512), 0, st, a);
+  } else {
+    return -1;
+  }
   return 0;
 }
 

@@ -58,6 +58,18 @@ grad and stored once for conv3's weight grad (conv1x1_bnin_fwd / conv1x1_bnin_dg
 AXform).  That removes one full read of each such tensor.  Measured: the backward form pays in
 layers 1-2 (default there), the forward form does not (off by default; see the flags below).
 
+The downsample BN's backward by Gram algebra (DPE_BND_GRAM=1, default; stride-1 1x1 downsample convs with 64 or
+128 input channels that take the BN3 Gram path -- ResNet-50's layer1.0): hd = x W_d^T is linear in the block input
+x exactly as h3 is in a2, so the forward adds one Gram pass over x (G_x, s_x, centred on a pilot shift sampled from
+x) and keeps u_d = W_d G_x; the backward forms P_d = dz3^T x (the downsample weight-grad GEMM, of dz3 instead of
+dhd), takes dgamma_d / dbeta_d / dW_d from bn_gram_bwd and the branch's data grad from the concatenated-K streaming
+kernel ([dz3 | x] x [diag(a) W_d ; W_d^T diag(b) W_d] + c W_d), which conv1's data grad adds as its residual.  No
+dhd tensor, no bn_bwd_apply pass over (dz3, hd), hd is not kept for backward, and the next block's data-grad
+epilogue emits the sum-dz partials only (it reads no hd).  The forward's outputs are unchanged.  The stride-2 form
+(layer2.0; DPE_BND_GRAM_S2=1, off by default: measured step-neutral) runs the Gram pass and the data grad's second
+segment over x[:, ::2, ::2] by row addressing and hands conv1's streaming data grad the compact [N, H/2, W/2, Cin]
+grid to add at the even pixels.
+
 Weight gradients are accumulated straight into the DDP bucket views and each
 parameter is announced to the reducer as soon as its gradient is final, in
 reverse-forward order, so bucket all-reduces start while earlier blocks are
@@ -107,6 +119,17 @@ _AX_TILE = int(os.environ.get("DPE_AX_TILE", "256"))
 # so there is no bn_bwd_apply pass and the next block's data-grad epilogue reads no h3.  For blocks whose
 # conv3 runs on the streaming pointwise kernel and whose successor chains BN3's backward.
 _GRAM = _BN3_CHAIN and os.environ.get("DPE_BN3_GRAM", "1") != "0"
+# DPE_BND_GRAM=0: the downsample BN's backward through bn_bwd_partials(dz3, hd) + weight grad + accumulating data
+# grad (bit for bit the path before the Gram form; A/B reference).  On: by Gram algebra over the block input (module
+# docstring) where bnd_gram_ok holds -- 1x1 stride-1 downsample convs with 64 / 128 input channels in blocks on the
+# BN3 Gram path (ResNet-50: layer1.0).  Measurements: docs/perf_notes.md.
+_BND_GRAM = _GRAM and os.environ.get("DPE_BND_GRAM", "1") != "0"
+# DPE_BND_GRAM_S2=1: the same for stride-2 downsample convs of up to 256 input channels (ResNet-50: layer2.0; the
+# Gram pass and the data grad's second segment address x[:, ::2, ::2] by rows).  Off: step-neutral as built -- the
+# apply pass (196 us), the hd read of the successor's epilogue (~50 us) and the compact data grad (150 us) go, but the
+# concatenated-K data grad runs on the implicit GEMM's AX_CAT tiles at 301 us (28 % of its byte bound) and the
+# strided Gram pass + pilot cost 111 us (docs/perf_notes.md); kept as a tested building block.
+_BND_GRAM_S2 = _BND_GRAM and os.environ.get("DPE_BND_GRAM_S2", "0") == "1"
 
 
 def _ax_ok(conv, cin) -> bool:
@@ -216,6 +239,7 @@ class BottleneckFn(Function):
         # the next block's fused data-grad epilogue reads this output's ReLU mask as bits
         want_bits = True  # 1/16 of out: read by the next block's fused epilogue or by this block's BN3 backward
         gram = None
+        bnd = None  # (u_d, s_x): the downsample BN's backward runs by Gram algebra
         # gram_next < 0: the successor is a downsample block, which chains this block's BN3 backward only
         # when its strided conv1 data grad can take the residual (the successor's own strided_ok test)
         out_shape = [*h2.shape[:3], convs[2].conv.out_channels]
@@ -235,6 +259,17 @@ class BottleneckFn(Function):
                 out, bits = C.conv1x1_apply(src, ws[2], src_coef, c3, x, None)
             h3 = None
             gram = (u3, sv, M3)
+            dconv = block.down.conv if block.down is not None else None
+            if (_BND_GRAM and dconv is not None and tuple(dconv.kernel_size) == (1, 1) and tuple(dconv.padding) == (0, 0)
+                    and C.bnd_gram_ok(list(x.shape), dconv.out_channels, list(dconv.stride))
+                    and (tuple(dconv.stride) == (1, 1) or (_BND_GRAM_S2 and tuple(convs[0].conv.stride) == (1, 1) and
+                         C.pw_dgrad_strided_residual_ok(list(x.shape), convs[0].conv.out_channels)))):
+                # BN_d's backward by Gram algebra: G_x, s_x of the plain block input (stride 2: of the pixels the
+                # downsample conv reads, x[:, ::2, ::2], by row addressing), centred on a pilot shift sampled from
+                # x itself (x has no producing BN here); only u_d = W_d G_x and s_x are kept
+                s2 = tuple(dconv.stride) == (2, 2)
+                Gx, sx = C.bn_gram(x, None, C.bn_gram_pilot(x, s2), s2)
+                bnd = (C.bn_gram_u(Gx, ws[3]), sx)
         else:
             h3, c3 = conv_coef(2, h2, c2) if a2 is None else conv_coef(2, a2)
         if gram is not None:
@@ -248,7 +283,8 @@ class BottleneckFn(Function):
             out, bits = C.bn_apply(h3, c3, hd, cd, True, want_bits)
         else:
             out, bits = C.bn_apply(h3, c3, x, None, True, want_bits)
-        ctx.save_for_backward(x, h1, a1, h2, a2, h3, out, hd, c1, c2, c3, cd)
+        # (the Gram backward of BN_d reads no hd: not kept)
+        ctx.save_for_backward(x, h1, a1, h2, a2, h3, out, None if bnd is not None else hd, c1, c2, c3, cd)
         # previous block's BN3 is fused into this block's first data grad.  A downsample block's dx also
         # has the stride-2 branch's term: it is computed first as a compact [N, H/2, W/2, C] data grad
         # and added at the even pixels by the streaming conv1 data grad's epilogue, which then applies
@@ -266,10 +302,11 @@ class BottleneckFn(Function):
         ctx.link_out = link_out
         ctx.bits = bits  # ReLU mask of out as bits: the standalone BN3 backward reads these, not out
         ctx.gram = gram
+        ctx.bnd = bnd
         if link_out is not None:
             link_out.h3, link_out.coef, link_out.mask = h3, c3, bits
             link_out.gram = gram is not None
-            if gram is not None and block.down is not None:
+            if gram is not None and block.down is not None and bnd is None:
                 # the next block's data-grad epilogue reduces the downsample BN's partials instead
                 # (sum dz, sum dz*(hd - mean_d)): row 0 serves BN3's Gram backward, both rows BN_d's
                 link_out.h3, link_out.coef = hd, cd
@@ -365,8 +402,29 @@ class BottleneckFn(Function):
             bn_done(bn, gb, gd, bb, bd)
             grad_done(w3, wdirect)
             grads[id(w3)] = None if wdirect else wbuf
-            dhd = None
-            if has_down and lk.h3 is not None:  # BN_d's partials came with dz3 (forward: link_out.h3 = hd)
+            dhd = dxd = None
+            bnd, ctx.bnd = ctx.bnd, None
+            if bnd is not None:
+                # BN_d by Gram algebra: P_d = dz3^T x (fixed-order split sums: dgamma_d comes from it), then the
+                # coefficient kernels write dgamma_d / dbeta_d / dW_d and the branch's data grad runs over the
+                # concatenated K [dz3 | x]; no dhd tensor
+                ud, sx = bnd
+                wd = convs[3].conv.weight
+                sd, pd, dd = _conv_conf(convs[3].conv)
+                Pd = torch.empty(wd.shape, dtype=torch.float32, device=wd.device)
+                C.conv_wgrad(dz3, x, Pd, sd, pd, dd, 1.0, None, deterministic=True, overwrite=True)
+                bn, gb, gd, bb, bd = bn_sinks(3)
+                dbuf, ddirect = grad_sink(wd)
+                bcat_d, ebias_d = C.bn_gram_bwd(lk.part, Pd, ws[3], ud, sx, cd, bn.weight.detach(),
+                                                dz3.numel() // dz3.shape[-1], gb, bb, dbuf)
+                bn_done(bn, gb, gd, bb, bd)
+                grad_done(wd, ddirect)
+                grads[id(wd)] = None if ddirect else dbuf
+                # (dxd: the branch's dx term, added by conv1's data grad as its residual; stride 2: the compact
+                # [N, H/2, W/2, Cin] grid, added at the even pixels)
+                dxd = (C.conv1x1_dgrad_cat_plain(dz3, x, bcat_d, ebias_d, sd[0] == 2) if ctx.needs_input_grad[0]
+                       else None)
+            elif has_down and lk.h3 is not None:  # BN_d's partials came with dz3 (forward: link_out.h3 = hd)
                 bn, gb, gd, bb, bd = bn_sinks(3)
                 dhd = C.bn_bwd_partials(dz3, hd, bn.weight.detach(), cd, lk.part, gb, bb, relu_mask=False)
                 bn_done(bn, gb, gd, bb, bd)
@@ -379,7 +437,7 @@ class BottleneckFn(Function):
             dh2 = C.bn_bwd_partials(da2, h2, bn.weight.detach(), c2, part2, gb, bb)
             bn_done(bn, gb, gd, bb, bd)
             return BottleneckFn._backward_tail(ctx, C, dz3, None, dh2, grads, bn_sinks, bn_done, bn_bwd, wgrad, dgrad,
-                                               dgrad_bnb, dhd)
+                                               dgrad_bnb, dhd, bnd is not None, dxd)
         if chained:
             # the next block's dgrad epilogue already produced dz3 = dout*relu'(out) and BN3's partials
             dz3 = dout
@@ -429,8 +487,11 @@ class BottleneckFn(Function):
                                            dgrad_bnb, dhd)
 
     @staticmethod
-    def _backward_tail(ctx, C, dz3, res_mask, dh2, grads, bn_sinks, bn_done, bn_bwd, wgrad, dgrad, dgrad_bnb, dhd=None):
-        """conv2 / conv1 / downsample gradients and dx, from dh2 (shared by the BN3 paths)."""
+    def _backward_tail(ctx, C, dz3, res_mask, dh2, grads, bn_sinks, bn_done, bn_bwd, wgrad, dgrad, dgrad_bnb, dhd=None,
+                       down_done=False, dxd=None):
+        """conv2 / conv1 / downsample gradients and dx, from dh2 (shared by the BN3 paths).  ``down_done``: the
+        downsample branch's parameter gradients are written already (BN_d by Gram algebra) and ``dxd`` is its
+        data grad."""
         x, h1, a1, h2, a2, h3, out, hd, c1, c2, c3, cd = ctx.saved_tensors
         convs, ws = ctx.convs, ctx.ws
         has_down = len(convs) == 4
@@ -441,7 +502,29 @@ class BottleneckFn(Function):
         dh1 = dgrad_bnb(1, dh2, 0, a1, h1, c1)  # (a1 unused: _EPI_BNB recomputes the mask from h1)
         wgrad(0, dh1, x)
         dx = None
-        if ctx.needs_input_grad[0]:
+        if down_done:
+            s2 = convs[3].conv.stride[0] == 2
+            li = ctx.link_in
+            assert li is None or s2, "a stride-1 downsample block is never chained from the previous block"
+            if dxd is None:
+                pass
+            elif not s2:
+                dx = dgrad(0, dh1, list(x.shape), dxd)
+            else:
+                # the streaming conv1 data grad adds the compact dxd at the even pixels; chained from the previous
+                # block it also applies that block's mask and emits its BN3 partials, as below
+                s, p, d = _conv_conf(convs[0].conv)
+                if li is None:
+                    dx = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, None, None, None, None, True)[0]
+                elif li.gram and li.h3 is None:
+                    dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, None, None, None, None, True,
+                                               li.mask)
+                else:
+                    dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, li.h3, li.coef, li.mask, None,
+                                               True)
+                if li is not None:
+                    li.part, li.dz_ptr, li.dz_shape = part, dx.data_ptr(), tuple(dx.shape)
+        elif ctx.needs_input_grad[0]:
             if has_down and ctx.link_in is not None:
                 if dhd is None:
                     dhd, _ = bn_bwd(3, dz3, None, hd, cd, False)
