@@ -138,6 +138,7 @@ int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, i
                  hipStream_t st);
 int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                  float* dq_acc, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, hipStream_t st);
+int dpe_set_attn_staged(int on);
 }
 
 namespace {
@@ -2183,24 +2184,29 @@ void layernorm_bwd_finalize_group(const std::vector<Tensor>& parts, const std::v
 }
 
 // ---------------------------------------------------------------- attention
-// qkv: [B, T, 3, H, D] bf16 -> out [B, T, H, D] bf16, lse [B, H, T] f32
-std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal) {
+// qkv: [B, T, 3, H, D] bf16 -> out [B, T, H, D] bf16, lse [B, H, T] f32 (both optionally caller-allocated)
+std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal, const c10::optional<Tensor>& out_,
+                             const c10::optional<Tensor>& lse_) {
   CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_CONTIG(qkv);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   TORCH_CHECK(qkv.numel() == B * T * 3 * H * D, "attn: qkv must be [B,T,3,H,D]");
   TORCH_CHECK(D == 64, "attn: head dim 64 supported");
-  Tensor out = at::empty({B, T, H, D}, qkv.options());
-  Tensor lse = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
+  Tensor out = (out_.has_value() && out_->defined()) ? *out_ : at::empty({B, T, H, D}, qkv.options());
+  Tensor lse = (lse_.has_value() && lse_->defined()) ? *lse_ : at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
+  CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out); CHECK_GPU(lse); CHECK_F32(lse); CHECK_CONTIG(lse);
+  TORCH_CHECK(out.numel() == B * T * H * D && lse.numel() == B * H * T, "attn_fwd: out is [B,T,H,D], lse [B,H,T]");
   CHECK_RC(dpe_attn_fwd(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal, cur_stream()),
            "attn_fwd");
   return {out, lse};
 }
 
 Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const Tensor& lse, int64_t H, double scale,
-                bool causal) {
+                bool causal, const c10::optional<Tensor>& dqkv_) {
   CHECK_GPU(qkv); CHECK_BF16(dout); CHECK_CONTIG(dout); CHECK_CONTIG(out);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
-  Tensor dqkv = at::empty_like(qkv);
+  Tensor dqkv = (dqkv_.has_value() && dqkv_->defined()) ? *dqkv_ : at::empty_like(qkv);
+  CHECK_GPU(dqkv); CHECK_BF16(dqkv); CHECK_CONTIG(dqkv);
+  TORCH_CHECK(dqkv.numel() == qkv.numel(), "attn_bwd: dqkv must have qkv's size");
   Tensor delta = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
   CHECK_RC(dpe_attn_bwd(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), nullptr, bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
                         (float)scale, causal, cur_stream()), "attn_bwd");
@@ -2431,9 +2437,13 @@ void register_ops(pybind11::module& m) {
   m.def("set_wgrad_hgemm", &set_wgrad_hgemm, "1x1 conv weight grads on the persistent hgemm kernel on/off");
   m.def("set_hgemm_conv", &set_hgemm_conv,
         "3x3 forward-form convs with >= 256 output channels on the persistent GEMM (implicit im2col A) on/off");
-  m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("causal") = true);
+  m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("causal") = true,
+        py::arg("out") = py::none(), py::arg("lse") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("H"),
-        py::arg("scale"), py::arg("causal") = true);
+        py::arg("scale"), py::arg("causal") = true, py::arg("dqkv") = py::none());
+  m.def("set_attn_staged", [](bool on) { return dpe_set_attn_staged(on ? 1 : 0) != 0; }, py::arg("on"),
+        "attention on the register-staged kernels instead of the LDS-DMA ones (test switch; default off); returns the "
+        "previous setting");
   m.def("set_gemm_backend", [](int64_t mode) {
           TORCH_CHECK(mode == 1, "only the native MFMA GEMM backend exists (mode 1); the vendor-library arm was removed");
         }, "kept for API compatibility: 1 = native kernels (the only backend)");

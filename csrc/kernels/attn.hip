@@ -1106,6 +1106,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
 
 using namespace dpe;
 
+// Run-time switch (set_attn_staged): take the register-staged kernels where the LDS-DMA ones would fit,
+// so the pair that normally serves only sequences of >= 2^31 bytes of qkv rows can be tested at any size.
+static int g_attn_staged = 0;
+extern "C" int dpe_set_attn_staged(int on) {
+  const int was = g_attn_staged;
+  g_attn_staged = on ? 1 : 0;
+  return was;
+}
+
 extern "C" int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int causal,
                             hipStream_t st) {
   if (D != AD || T % AKV != 0 || !causal) return -1;
@@ -1114,7 +1123,7 @@ extern "C" int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int 
   hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
 #else
   // one sequence's qkv rows must fit the DMA kernel's 32-bit buffer range
-  if ((int64_t)T * 3 * H * AD * 2 < (1LL << 31))
+  if (!g_attn_staged && (int64_t)T * 3 * H * AD * 2 < (1LL << 31))
     hipLaunchKernelGGL(attn_fwd_dma_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, lse, B, T, H,
                        sl2);
   else
@@ -1129,29 +1138,27 @@ extern "C" int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint
   (void)dq_acc;  // dQ is not accumulated with atomics (attn_bwd_dq_kernel)
   if (D != AD || T % AKV != 0 || !causal) return -1;
   const float sl2 = scale * 1.4426950408889634f;
+  // one sequence's qkv / dO rows must fit the DMA kernels' 32-bit buffer ranges
+  const bool dma = !g_attn_staged && (int64_t)T * 3 * H * AD * 2 < (1LL << 31);
   // dQ first: it also writes delta = rowsum(dO * O), which the dK/dV kernel reads
 #ifdef DPE_ATTN_BWD_STAGED
   hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse, delta,
                      dqkv, B, T, H, sl2, scale);
-#else
-  if ((int64_t)T * 3 * H * AD * 2 < (1LL << 31))
-    hipLaunchKernelGGL(attn_bwd_dq_dma_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse,
-                       delta, dqkv, B, T, H, sl2, scale);
-  else
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse, delta,
-                       dqkv, B, T, H, sl2, scale);
-#endif
-#ifdef DPE_ATTN_BWD_STAGED
   hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * H * ((T + BKW - 1) / BKW)), dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B,
                      T, H, sl2, scale);
+  (void)dma;
 #else
-  // one sequence's qkv / dO rows must fit the DMA kernel's 32-bit buffer ranges
-  if ((int64_t)T * 3 * H * AD * 2 < (1LL << 31))
+  if (dma) {
+    hipLaunchKernelGGL(attn_bwd_dq_dma_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse,
+                       delta, dqkv, B, T, H, sl2, scale);
     hipLaunchKernelGGL(attn_bwd_dma_kernel, dim3(B * H * ((T + BKW - 1) / BKW)), dim3(256), 0, st, qkv, dout, lse, delta,
                        dqkv, B, T, H, sl2, scale);
-  else
+  } else {
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse, delta,
+                       dqkv, B, T, H, sl2, scale);
     hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * H * ((T + BKW - 1) / BKW)), dim3(256), 0, st, qkv, dout, lse, delta, dqkv,
                        B, T, H, sl2, scale);
+  }
 #endif
   return 0;
 }

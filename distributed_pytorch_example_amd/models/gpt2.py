@@ -64,7 +64,9 @@ class Block(nn.Module):
             lin.weight._dpe_overwrite_ok = True
 
     def forward(self, x):
-        if x.is_cuda and self.fused and torch.is_grad_enabled():
+        # (the fused block calls the attention kernels directly: only for the shapes they take)
+        if (x.is_cuda and self.fused and torch.is_grad_enabled()
+                and Fx.attn_kernel_ok(x.shape[1], x.shape[2] // self.n_head)):
             from ._gpt2_fused import block_forward  # hand-scheduled fwd/bwd, one autograd node
 
             return block_forward(self, x)

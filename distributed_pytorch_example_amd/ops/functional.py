@@ -651,6 +651,22 @@ class _AttnFn(Function):
         return dqkv, None, None
 
 
+def attn_kernel_ok(T: int, D: int) -> bool:
+    """The shapes the flash-attention kernels take (csrc/kernels/attn.hip): head dim 64, whole 64-key tiles."""
+    return D == 64 and T % 64 == 0
+
+
+def _causal_attention_torch(qkv5, scale: float):
+    """Shapes outside the kernels' range: explicit masked softmax(Q K^T) V in fp32 torch ops (autograd
+    differentiates it), result in qkv's dtype like the kernel's."""
+    q, k, v = qkv5.float().permute(2, 0, 3, 1, 4)  # each [B, H, T, D]
+    T = q.shape[-2]
+    s = (q @ k.transpose(-1, -2)) * scale
+    s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+    o = torch.softmax(s, dim=-1) @ v
+    return o.transpose(1, 2).to(qkv5.dtype)  # [B, T, H, D]
+
+
 def causal_attention(qkv, n_head: int):
     """qkv: [B, T, 3*H*D] -> [B, T, H*D] causal softmax attention."""
     B, T, three_hd = qkv.shape
@@ -660,6 +676,8 @@ def causal_attention(qkv, n_head: int):
         q, k, v = qkv.float().view(B, T, 3, n_head, D).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return o.transpose(1, 2).reshape(B, T, n_head * D)
+    if not attn_kernel_ok(T, D):
+        return _causal_attention_torch(qkv.reshape(B, T, 3, n_head, D), scale).reshape(B, T, n_head * D)
     out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale)
     return out.reshape(B, T, n_head * D)
 
