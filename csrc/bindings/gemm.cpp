@@ -24,15 +24,16 @@
 #include "../kernels/hgemm.h"
 #include "../kernels/igemm.h"
 #include "gemm_plan.h"
+#include "ops_common.h"
 
 using at::Tensor;
 
-extern "C" int dpe_cu_reserve();  // comm.cpp: slots to leave to in-flight collectives
-
 namespace dpe_gemm {
 
+using dpe_ops::cur_stream;
+using dpe_ops::env_on;
+
 namespace {
-hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 struct TileCfg { int cfg, bm, bn, bpc; double eff, eff_alone; };
 // eff: per-CU throughput relative to the 256x256 tile with the CU fully occupied (bpc blocks);
@@ -58,8 +59,8 @@ constexpr double kLaunch = 3.0e-6;
 int g_force_cfg = -1, g_force_splits = -1;
 // (off by default: with it the budgeted planner traded whole-K plans for K splits whose slab traffic
 // cost more than the balance bought -- GPT-2 data grads x1.7 -> x3.0, profiles/cu_hog_probe_r4.txt)
-bool g_budget_tail = [] { const char* e = getenv("DPE_HGEMM_BUDGET_TAIL"); return e && e[0] == '1'; }();  // A/B
-bool g_dynamic = [] { const char* e = getenv("DPE_HGEMM_DYNAMIC"); return !(e && e[0] == '0'); }();  // A/B
+bool g_budget_tail = env_on("DPE_HGEMM_BUDGET_TAIL", false);  // A/B
+bool g_dynamic = env_on("DPE_HGEMM_DYNAMIC", true);  // A/B
 
 // Dynamic-schedule state of the persistent GEMM (hgemm.hip: 8 per-XCD claim counters + exit
 // counters), one zeroed buffer per (device, stream): launches on one stream are ordered, and the last
@@ -122,7 +123,7 @@ unsigned* sk_counters(hipStream_t st) {
 // filled round runs faster per CU, so the idle CUs cost less than their share.  Off by default: its owners
 // wait on blocks of their own grid, which an RCCL kernel holding CUs can delay by a whole all-reduce
 // (docs/perf_notes.md).
-int g_sk = [] { const char* e = getenv("DPE_HGEMM_SK"); return (e && e[0] == '1') ? 1 : 0; }();
+int g_sk = env_on("DPE_HGEMM_SK", false) ? 1 : 0;
 
 unsigned* sched_buffer(hipStream_t st) { return sched_buffer_impl(st); }
 
@@ -212,7 +213,7 @@ Plan2 plan2(int64_t M, int64_t N, int64_t K, int ak, int bk, bool allow_split, i
   Plan2 best;
   best.main = plan(M, N, K, ak, bk, allow_split, out_bytes);
   best.est_s = best.main.est_s;
-  static const bool on = [] { const char* e = getenv("DPE_HGEMM_PLAN2"); return !(e && e[0] == '0'); }();  // A/B
+  static const bool on = env_on("DPE_HGEMM_PLAN2", true);  // A/B
   if (!on || best.main.cfg < 0 || g_force_cfg >= 0 || g_force_splits >= 0) return best;
   const int ncu = num_cus();
   const int reserve = dpe_cu_reserve();
@@ -294,8 +295,7 @@ void launch_planned(dpe::HgemmArgs a, const Plan& pl, int ak, int bk, int epi, h
     }
     // DPE_AB_SKIP_FINALIZE=1: timing diagnostic only (what the slab reductions cost the step; gradients WRONG)
     static const bool skip = [] {
-      const char* e = getenv("DPE_AB_SKIP_FINALIZE");
-      const bool on = e && e[0] == '1';
+      const bool on = env_on("DPE_AB_SKIP_FINALIZE", false);
       if (on) fprintf(stderr, "[dpe] DPE_AB_SKIP_FINALIZE=1: K-split weight gradients are NOT reduced (timing only)\n");
       return on;
     }();
@@ -398,14 +398,6 @@ void run_bnb(dpe::HgemmArgs& a, const Plan& pl, int ak, int bk) {
   launch_planned(a, pl, ak, bk, dpe::HE_BF16, nullptr);
 }
 
-}  // namespace dpe_gemm
-
-extern "C" int dpe_gemm_f32(const float* A, const float* B, float* C, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,
-                            int64_t ldc, int M, int N, int K, const float* bias, float alpha, int relu, float drop_p,
-                            uint64_t seed, uint64_t offset, const float* mask_src, float mask_scale, int accumulate,
-                            hipStream_t st);
-
-namespace dpe_gemm {
 namespace {
 
 // ------------------------------------------------ fp32 Linear (exact-f32 MFMA, gemm_f32.hip)

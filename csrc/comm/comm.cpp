@@ -22,8 +22,7 @@
 
 #include <pybind11/functional.h>
 
-extern "C" int dpe_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t st);
-extern "C" int dpe_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t st);
+#include "../kernels/launch.h"  // dpe_cu_reserve (defined here), dpe_cast_*
 
 // persistent-kernel slots to leave free right now (0 unless a collective may be resident)
 extern "C" int dpe_cu_reserve() {

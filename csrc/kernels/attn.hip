@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 

@@ -14,6 +14,7 @@
 // the stats pass is skipped entirely.
 #include <cstdlib>
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 

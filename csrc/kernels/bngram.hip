@@ -24,6 +24,7 @@
 #include <utility>
 
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 namespace gram {

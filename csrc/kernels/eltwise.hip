@@ -3,6 +3,7 @@
 // from (seed, offset) -- no mask tensor), residual add, bias-grad column
 // sums, NCHW->NHWC input packing, embedding gather / scatter-add.
 #include "common.h"
+#include "launch.h"
 #include <algorithm>
 
 namespace dpe {
@@ -252,7 +253,7 @@ __global__ __launch_bounds__(256) void conv_w_flipT_kernel(const uint16_t* __res
 }
 
 // Several flips in ONE launch (the data grads of a backward pass refresh all their flipped filters at
-// once, ops.cpp flipped()): block b belongs to entry e with start[e] <= b < start[e + 1], and runs
+// once, conv.cpp flipped()): block b belongs to entry e with start[e] <= b < start[e + 1], and runs
 // conv_w_flipT_kernel's block (b - start[e]) of that entry.
 struct FlipDesc {
   const uint16_t* w;

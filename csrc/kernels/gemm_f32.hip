@@ -17,6 +17,7 @@
 //           layer's relu+dropout, read from its saved output (y > 0 <=> kept and positive)
 //   wgrad : dw += alpha * acc                        (fp32 gradient bucket views)
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 namespace g32 {

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 

@@ -4,6 +4,7 @@
 //      per block into partials, then summed (+=) into the fp32 grads.
 //      dx is either written (x dtype) or ACCUMULATED into an f32 residual-stream grad.
 #include "common.h"
+#include "launch.h"
 
 #define DPE_LN_FIN_GROUP_MAX 8
 namespace dpe {

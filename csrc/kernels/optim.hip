@@ -11,6 +11,7 @@
 // Hyper-parameters (lr etc.) live in a small device array so a captured
 // hipGraph can replay the step while the host edits the learning rate.
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 

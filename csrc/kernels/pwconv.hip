@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "igemm.h"
+#include "launch.h"
 #include "pwconv.h"
 
 namespace dpe {
@@ -695,8 +696,6 @@ __global__ __launch_bounds__(64 * (K2 / 16), K2 == 64 ? 2 : 1) void pw_cat_kerne
 
 using namespace dpe;
 
-extern "C" int dpe_cu_reserve();  // comm.cpp
-
 // blocks of the concatenated-K data grad: the resident capacity (2 x 4-wave blocks per CU at K2 = 64,
 // 1 x 8-wave at 128), twice that while a CU budget is in force (two dispatch rounds: the CUs that share
 // with RCCL's blocks get fewer); 0 outside (K1, K2) in {(256, 64), (512, 128)} or a row count whose
@@ -730,8 +729,6 @@ extern "C" int dpe_pw_cat_launch(const PwCatArgs* args, int64_t K1, int64_t K2, 
   }
   return 0;
 }
-
-extern "C" int dpe_cu_reserve();  // comm.cpp
 
 // columns per wave.  The data grads at K = 64 / 128 use 32 (like K = 256) so that the epilogue operands
 // (residual, pre-BN input, masks) can be hoisted ahead of the tile's MFMAs: with 64 columns per wave

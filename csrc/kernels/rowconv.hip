@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 namespace rowconv {
@@ -495,8 +496,6 @@ __global__ __launch_bounds__(256) void wgrad3x3_rows_sum_kernel(const float* __r
 }  // namespace wg
 }  // namespace rowconv
 }  // namespace dpe
-
-extern "C" int dpe_cu_reserve();  // comm.cpp: slots left to in-flight collectives
 
 namespace {
 int rows_slots() {  // resident blocks of the row-walking kernels (2 per CU), minus the CU budget

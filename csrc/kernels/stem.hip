@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "launch.h"
 
 namespace dpe {
 namespace stem {
@@ -532,8 +533,6 @@ extern "C" int dpe_stem_launch(const uint16_t* x, const uint16_t* w, uint16_t* y
   hipLaunchKernelGGL(dpe::stem::stem_conv_kernel, dim3(nb), dim3(256), 0, st, x, w, y, stats, H, W, 3);
   return (int)hipGetLastError();
 }
-
-extern "C" int dpe_cu_reserve();  // comm.cpp
 
 // Blocks per image of the stem weight grad: 2 (half-image blocks) while a CU budget is in force
 // (collectives in flight: two dispatch rounds balance around their workgroups), else 1.

@@ -65,7 +65,7 @@ _weight_epoch = [0]
 
 
 def bump_weight_epoch() -> None:
-    """The bf16 shadows changed: the native cached flipped filters (ops.cpp flipped()) refresh at next use."""
+    """The bf16 shadows changed: the native cached flipped filters (conv.cpp flipped()) refresh at next use."""
     _weight_epoch[0] += 1
     try:
         from ._ext import ext
