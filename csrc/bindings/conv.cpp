@@ -690,13 +690,21 @@ std::vector<Tensor> conv_fwd(const Tensor& x, const Tensor& w, std::vector<int64
 // DPE_DGRAD_FWD=0: stride-1 data grads on the transposed-filter loaders (A/B reference)
 bool dgrad_as_fwd() { static const bool on = env_on("DPE_DGRAD_FWD", true); return on; }
 
+void conv_wgrad(const Tensor& dy, const Tensor& x, Tensor& dw, std::vector<int64_t> stride, std::vector<int64_t> pad,
+                std::vector<int64_t> dil, double alpha, const c10::optional<Tensor>& in_coef, int64_t fin_stream,
+                bool deterministic, bool overwrite);
+
 std::vector<Tensor> conv_dgrad_impl(const Tensor& dy, const Tensor& w, std::vector<int64_t> xshape,
                                     std::vector<int64_t> stride, std::vector<int64_t> pad, std::vector<int64_t> dil,
                                     const c10::optional<Tensor>& residual, const c10::optional<Tensor>& bn_x,
                                     const c10::optional<Tensor>& bn_coef, const Tensor* acc_into = nullptr,
                                     const c10::optional<Tensor>& bn_mask = c10::nullopt,
                                     const c10::optional<Tensor>& residual_mask = c10::nullopt,
-                                    bool res_stride2 = false, const c10::optional<Tensor>& sum_mask = c10::nullopt) {
+                                    bool res_stride2 = false, const c10::optional<Tensor>& sum_mask = c10::nullopt,
+                                    const c10::optional<Tensor>& p_src = c10::nullopt,
+                                    const c10::optional<Tensor>& p_coef = c10::nullopt) {
+  TORCH_CHECK(!has(p_src) || has(sum_mask), "conv_dgrad: p_src needs sum_mask");
+  TORCH_CHECK(!has(p_coef) || has(p_src), "conv_dgrad: p_coef needs p_src");
   CHECK_GPU(dy); CHECK_BF16(dy); CHECK_BF16(w); CHECK_CONTIG(dy); CHECK_CONTIG(w);
   // acc_into: dx += dgrad in place (the epilogue reads each element as its residual
   // right before overwriting it); parities no tap reaches are left untouched.
@@ -766,7 +774,23 @@ std::vector<Tensor> conv_dgrad_impl(const Tensor& dy, const Tensor& w, std::vect
     CHECK_CONTIG((*sum_mask));
     TORCH_CHECK(sum_mask->scalar_type() == at::kByte && sum_mask->numel() * 8 == dx.numel() && g.C % 8 == 0,
                 "conv_dgrad: sum_mask must be uint8 mask bits [N,H,W,C/8] of dx's shape");
-    const int rg = pw_stream_on() ? dpe_pw_rowgroups(a.M, a.N, a.K, dpe::PW_DSUM) : 0;
+    // p_src (+ p_coef): also P = dx^T a2 [C, 1, 1, k2] fp32, a2 = relu(BN(p_src)) or p_src itself -- the BN3 Gram
+    // backward's dz3^T a2, formed by the epilogue that stores dx (inside dpe_pw_p_rowgroups' envelope; outside
+    // it the deterministic weight grad over the stored dx)
+    int64_t k2 = 0;
+    int rgp = 0;
+    if (has(p_src)) {
+      CHECK_GPU((*p_src)); CHECK_BF16((*p_src)); CHECK_CONTIG((*p_src));
+      TORCH_CHECK(p_src->dim() == 4 && p_src->size(0) == g.N && p_src->size(1) == g.H && p_src->size(2) == g.W,
+                  "conv_dgrad: p_src must be [N, H, W, k2] over dx's pixels");
+      k2 = p_src->size(3);
+      if (has(p_coef)) {
+        CHECK_F32((*p_coef)); CHECK_CONTIG((*p_coef));
+        TORCH_CHECK(p_coef->numel() == 4 * k2, "conv_dgrad: p_coef must be [4][k2]");
+      }
+      rgp = pw_stream_on() ? dpe_pw_p_rowgroups(a.M, a.N, a.K, k2) : 0;
+    }
+    const int rg = rgp > 0 ? rgp : (pw_stream_on() ? dpe_pw_rowgroups(a.M, a.N, a.K, dpe::PW_DSUM) : 0);
     TORCH_CHECK(rg > 0, "conv_dgrad: sum_mask needs the streaming pointwise data grad");
     dpe::PwArgs pa{};
     pa.x = bp(dy); pa.w = bp(w); pa.y = bpm(dx);
@@ -776,7 +800,21 @@ std::vector<Tensor> conv_dgrad_impl(const Tensor& dy, const Tensor& w, std::vect
     pa.M = a.M; pa.N = a.N; pa.K = a.K; pa.rg = rg; pa.sched = dpe_gemm::sched_buffer(cur_stream());
     part = at::empty({2, g.C, rg}, dy.options().dtype(at::kFloat));
     pa.stats = fp(part);
+    Tensor slab;
+    if (rgp > 0) {
+      slab = at::empty({rg, g.C, k2}, dy.options().dtype(at::kFloat));
+      pa.p_src = bp(*p_src);
+      pa.p_coef = has(p_coef) ? fp(*p_coef) : nullptr;
+      pa.p_slab = fp(slab);
+      pa.p_k2 = (int)k2;
+    }
     CHECK_RC(dpe_pw_launch(&pa, dpe::PW_DSUM, cur_stream()), "pw_stream dgrad (sum dz)");
+    if (has(p_src)) {
+      Tensor P = at::empty({g.C, 1, 1, k2}, dy.options().dtype(at::kFloat));
+      if (rgp > 0) CHECK_RC(dpe_pw_p_reduce(fp(slab), rg, (int64_t)g.C * k2, fp(P), cur_stream()), "pw_stream P reduce");
+      else conv_wgrad(dx, *p_src, P, {1, 1}, {0, 0}, {1, 1}, 1.0, p_coef, 0, true, true);
+      return {dx, part, P};
+    }
     return {dx, part};
   }
   if (pw_rg > 0) {
@@ -1073,19 +1111,28 @@ void register_conv(pybind11::module& m) {
           if (xshape.size() != 4 || xshape[1] % 2 || xshape[2] % 2 || !pw_stream_on()) return false;
           return dpe_pw_rowgroups(xshape[0] * xshape[1] * xshape[2], xshape[3], k, dpe::PW_DGRAD) > 0;
         }, py::arg("xshape"), py::arg("k"));
+  m.def("pw_dgrad_fused_p_ok", [](std::vector<int64_t> xshape, int64_t k, int64_t k2) {
+          // conv_dgrad_bn(..., sum_mask, p_src) of a 1x1 conv k -> xshape[3] forms P = dx^T a2 (k2 columns) in the
+          // streaming data grad's epilogue (else: by the deterministic weight grad over the stored dx)
+          if (xshape.size() != 4 || !pw_stream_on()) return false;
+          return dpe_pw_p_rowgroups(xshape[0] * xshape[1] * xshape[2], xshape[3], k, k2) > 0;
+        }, py::arg("xshape"), py::arg("k"), py::arg("k2"));
   m.def("conv_dgrad_acc", &conv_dgrad_acc, py::arg("dy"), py::arg("w"), py::arg("dx"), py::arg("stride"), py::arg("pad"),
         py::arg("dil"), "dx += data grad of conv(w) in place (parities without taps untouched)");
   m.def("conv_dgrad_bn", [](const Tensor& dy, const Tensor& w, std::vector<int64_t> xshape, std::vector<int64_t> stride,
                             std::vector<int64_t> pad, std::vector<int64_t> dil, const c10::optional<Tensor>& residual,
                             const c10::optional<Tensor>& bn_x, const c10::optional<Tensor>& bn_coef,
                             const c10::optional<Tensor>& bn_mask, const c10::optional<Tensor>& residual_mask,
-                            bool residual_stride2, const c10::optional<Tensor>& sum_mask) {
+                            bool residual_stride2, const c10::optional<Tensor>& sum_mask,
+                            const c10::optional<Tensor>& p_src, const c10::optional<Tensor>& p_coef) {
           return conv_dgrad_impl(dy, w, xshape, stride, pad, dil, residual, bn_x, bn_coef, nullptr, bn_mask, residual_mask,
-                                 residual_stride2, sum_mask);
+                                 residual_stride2, sum_mask, p_src, p_coef);
         }, py::arg("dy"), py::arg("w"), py::arg("xshape"), py::arg("stride"),
         py::arg("pad"), py::arg("dil"), py::arg("residual") = py::none(), py::arg("bn_x") = py::none(),
         py::arg("bn_coef") = py::none(), py::arg("bn_mask") = py::none(), py::arg("residual_mask") = py::none(),
-        py::arg("residual_stride2") = false, py::arg("sum_mask") = py::none(),
+        py::arg("residual_stride2") = false, py::arg("sum_mask") = py::none(), py::arg("p_src") = py::none(),
+        py::arg("p_coef") = py::none(),
+        "with sum_mask and p_src (+ p_coef): a third result P = dx^T relu(BN(p_src)) [C, 1, 1, k2] fp32 (fixed order); "
         "data grad; with bn_x/bn_coef also the BN-backward partials of the BN+ReLU that produced the conv input; "
         "with bn_mask (BN + residual + ReLU) the mask is bn_mask > 0 and dx is stored masked");
   m.def("conv_dgrad", &conv_dgrad, py::arg("dy"), py::arg("w"), py::arg("xshape"), py::arg("stride"), py::arg("pad"),

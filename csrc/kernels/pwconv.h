@@ -33,6 +33,12 @@ struct PwArgs {
   uint8_t* out_bits;         // PW_APPLY: ReLU bits of y ([M][N/8]), or nullptr
   unsigned* sched;           // claim counters (HGEMM_SCHED_BYTES, zeroed, left zeroed) for the dynamic schedule,
                              // or nullptr: static (see dpe_pw_rowgroups)
+  // PW_DSUM with the fused product P = y^T a2 (the BN3 Gram backward's dz3^T a2, from the rows this epilogue
+  // stores): p_k2 in {64, 128} columns of p_src; 0 = none
+  const uint16_t* p_src;     // [M][p_k2] bf16: the second operand's rows (the pre-BN h2, or a plain operand)
+  const float* p_coef;       // [4][p_k2]: the operand is bf16(relu(p_src * scale + shift)); nullptr = plain
+  float* p_slab;             // [rg][N][p_k2] fp32: one partial product per row group (dpe_pw_p_reduce sums them)
+  int p_k2;
 };
 
 // The concatenated-K data grad of the Gram-path BN3 backward (bngram.hip) on a streaming kernel:
@@ -65,3 +71,9 @@ extern "C" int dpe_pw_cat_launch(const dpe::PwCatArgs* args, int64_t K1, int64_t
 // rows and the last two thirds are claimed at run time (PwArgs::sched); otherwise one per resident block row.
 extern "C" int dpe_pw_rowgroups(int64_t M, int64_t N, int64_t K, int epi);
 extern "C" int dpe_pw_launch(const dpe::PwArgs* args, int epi, hipStream_t stream);
+
+// PW_DSUM with the fused product (PwArgs::p_src): row groups of that launch, or 0 outside its envelope
+// ((K, k2) in {(64, 64), (128, 64), (128, 128)} inside PW_DSUM's own).  The launch is dpe_pw_launch with
+// p_k2 = k2 and rg from here; dpe_pw_p_reduce then sums the slabs in row-group order: P[N][k2] fp32.
+extern "C" int dpe_pw_p_rowgroups(int64_t M, int64_t N, int64_t K, int64_t k2);
+extern "C" int dpe_pw_p_reduce(const float* slab, int rg, int64_t n, float* P, hipStream_t stream);

@@ -57,10 +57,35 @@ DPE_DEVICE void wait_vm() {  // s_waitcnt vmcnt(N): loads, LDS-DMA and stores co
   asm volatile("" ::: "memory");
 }
 
+// Fused P (K2 > 0 below): the a2 image's chunk swizzle (bngram.hip's gram_h: the transposed reads are
+// bank-conflict-free) and one MFMA operand from two transposing reads (rows r .. r + 3 and r + 4 .. r + 7 of
+// 16 channels: lane (g, 4 q + p) passes the addresses of rows 8 g + q and 8 g + q + 4, channels 4 p .. + 3)
+template <int C>
+DPE_DEVICE int p_h(int row) {
+  return C >= 128 ? ((row & 3) | (((row >> 3) & 1) << 2)) : (((row >> 1) & 1) | (((row >> 3) & 1) << 1));
+}
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
+DPE_DEVICE bf16x8 p_trfrag(const char* a1, const char* a2) {
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)a1);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)a2);
+  s16x8 r;
+  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
+  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
+  return __builtin_bit_cast(bf16x8, r);
+}
+
 // K: reduction depth; WN: output columns per wave (4 waves -> 4*WN per block); NS: ring depth
 // DYN: the dynamic row-group schedule (a compile-time variant: the static kernels keep their registers)
-template <int K, int WN, int NS, int EPI, bool DYN = false>
-__global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_stream_kernel(PwArgs a) {
+// K2 > 0 (PW_DSUM, WN = 32; a compile-time variant likewise): the epilogue also forms P = y^T a2 over the rows it
+// stores, a2 = bf16(relu(p_src * scale + shift)) [M][K2] (PwArgs::p_src): the wave's 32 columns x K2 accumulate
+// in registers over the row group (MFMA A = the half tile just staged, with the stored values written back
+// and rows past M zeroed, read transposed; B = the tile's p_src rows, LDS-DMA'd into one staged image with the
+// hoisted epilogue operands, transformed ONCE per block in place and read transposed by every wave), one
+// fp32 slab per row group -- the BN3 Gram backward's dz3^T a2 without re-reading dz3.  <64, 32, 4> with
+// K2 = 64 keeps the plain kernel's 3 blocks per CU (167 VGPRs), so a launch has the same row groups and
+// partials with or without P.
+template <int K, int WN, int NS, int EPI, bool DYN = false, int K2 = 0>
+__global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN))) ? 3 : 2) void pw_stream_kernel(PwArgs a) {
   constexpr int KC = K / 32;                  // 32-deep K chunks
   constexpr int TILE = BM * K * 2;            // bytes of one x tile in LDS ([KC][64 rows][64 B])
   constexpr int P = TILE / 1024 / 4;          // 1-KiB DMA pieces per wave per tile
@@ -78,7 +103,11 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
   // ONE LDS object: ring, staging, in_coef's [scale | shift] of the K input channels, the claim slot.  (With a
   // second __shared__ object the compiler cannot tell the ring DMA's LDS writes from the other accesses and
   // drains vmcnt(0) -- the next tile's DMA -- before each tile's fragment reads.)
-  __shared__ __attribute__((aligned(16))) char smem[NS * TILE + 4 * STG + 2 * K * 4 + 16];
+  constexpr bool PF = K2 > 0;
+  static_assert(!PF || (EPI == PW_DSUM && WN == 32 && (K2 == 64 || K2 == 128) && K2 <= K), "fused P: envelope");
+  // (PF: + the a2 image [64 rows][K2] bf16, 16-B chunk c of row r at c ^ 2 h(r) -- bngram.hip's layout)
+  constexpr int A2OFF = NS * TILE + 4 * STG + 2 * K * 4 + 16, A2RB = 2 * (PF ? K2 : 8);
+  __shared__ __attribute__((aligned(16))) char smem[A2OFF + (PF ? BM * A2RB : 0)];
   float* const bnin = (float*)(smem + NS * TILE + 4 * STG);
   int* const claim_slot = (int*)(smem + NS * TILE + 4 * STG + 2 * K * 4);
 
@@ -154,6 +183,17 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
   float s[8], ss[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
+  // PF: the wave's P[32 columns][K2] as NI x K2/16 MFMA fragments; the a2 image as PCPR 1-KiB DMA pieces of
+  // PRPP rows, PPW per wave (lane: row l / PCPR of the piece, physical chunk l % PCPR), each transformed by
+  // the lanes that loaded it
+  constexpr int PNJ = PF ? K2 / 16 : 1, PCPR = PF ? K2 / 8 : 8, PRPP = 64 / PCPR, PPW = PCPR / 4;
+  f32x4 pacc[NI][PNJ];
+  if constexpr (PF) {
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int nj = 0; nj < PNJ; ++nj) pacc[ni][nj] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   // PW_APPLY: the BN applied to this lane's 8 output channels (+ the residual's own BN)
   float osc[8], osh[8], rsc[8], rsh[8];
   if constexpr (EPI == PW_APPLY) {
@@ -190,9 +230,15 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
   const __amdgpu_buffer_rsrc_t xsrs = rsrc(a.st_x, bnx ? ybytes : 0u);
   const __amdgpu_buffer_rsrc_t smrs = rsrc(a.st_mask, (bnb && a.st_mask) ? mbytes : 0u);
   const __amdgpu_buffer_rsrc_t obrs = rsrc(a.out_bits, (EPI == PW_APPLY && a.out_bits) ? mbytes : 0u);
+  const __amdgpu_buffer_rsrc_t psrs = rsrc(a.p_src, PF ? (uint32_t)((int64_t)M * K2 * 2) : 0u);
 
   if (!DG && a.in_coef) {  // before the ring's first DMA (its counted waits start after this)
     for (int i = tid; i < 2 * K; i += 256) bnin[i] = a.in_coef[i];
+    __syncthreads();
+  }
+  if constexpr (PF) {  // a2's [scale | shift] in the (data grad: otherwise unused) table
+    if (a.p_coef)
+      for (int i = tid; i < 2 * K2; i += 256) bnin[i] = a.p_coef[i];
     __syncthreads();
   }
 
@@ -225,6 +271,20 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
             if (bnb && a.st_mask) hsmb[hf][ps] = __builtin_amdgcn_raw_buffer_load_b8(smrs, (uint32_t)(off >> 3), 0, 0);
           }
         }
+    }
+    // PF: the tile's p_src rows with the hoisted operands, by LDS-DMA into the a2 image (every wave is past the
+    // previous tile's reads of it: the ring barrier); unconditional, rows past M read as zeros; older than
+    // the ring DMAs issued below, so the counted waits hold
+    if constexpr (PF) {
+      int ol = lane;  // (opaque: see the fragment reads below)
+      asm volatile("" : "+v"(ol));
+#pragma unroll
+      for (int k = 0; k < PPW; ++k) {
+        const int q = wid * PPW + k, r = q * PRPP + ol / PCPR, lc = (ol % PCPR) ^ (2 * p_h<K2>(r));
+        const int m = m0 + r;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(psrs, (lds_void_t*)(smem + A2OFF + q * 1024), 16,
+                                                 m < M ? (uint32_t)(((int64_t)m * K2 + 8 * lc) * 2) : 0x80000000u, 0, 0, 0);
+      }
     }
     if (!DG && a.in_coef) {
       // BN + ReLU of the producer applied to the landed tile ONCE, cooperatively in LDS (every wave reads
@@ -269,6 +329,31 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni][kc], xf[mi], acc[mi][ni], 0, 0, 0);
+    }
+    if constexpr (PF) {
+      // the a2 image, once per block, in place: everything older than the P ring DMAs just issued has landed
+      // (the counted wait below is then a no-op); each lane transforms the chunks it loaded itself.  Rows past
+      // M: relu(shift) values -- their staged y rows are zero.
+      wait_vm<P>();
+      char* const a2 = smem + A2OFF;
+      if (a.p_coef) {
+        int ol = lane;  // (opaque: see the fragment reads below)
+        asm volatile("" : "+v"(ol));
+#pragma unroll
+        for (int k = 0; k < PPW; ++k) {
+          const int q = wid * PPW + k, r = q * PRPP + ol / PCPR, lc = (ol % PCPR) ^ (2 * p_h<K2>(r));
+          const f32x4 s0 = *(const f32x4*)(bnin + 8 * lc), s1 = *(const f32x4*)(bnin + 8 * lc + 4);
+          const f32x4 h0 = *(const f32x4*)(bnin + K2 + 8 * lc), h1 = *(const f32x4*)(bnin + K2 + 8 * lc + 4);
+          const float sc8[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+          const float sh8[8] = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+          u32x4* const pc = (u32x4*)(a2 + q * 1024 + ol * 16);
+          float f[8];
+          unpack8(*pc, f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[e] = fmaxf(fmaf(f[e], sc8[e], sh8[e]), 0.f);
+          *pc = pack8(f);
+        }
+      }
     }
     // y rows: lane holds channels n0w + 16 ni + 4 g + e of pixel m0 + 16 mi + li; staged per
     // 32-row half through the wave's LDS region (LDS ops of one wave complete in order, so the
@@ -382,8 +467,37 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
         }
         if constexpr (HOIST) __builtin_amdgcn_raw_buffer_store_b128(v, yrs, valid ? (uint32_t)(((int64_t)m * N + nch) * 2) : OOB, 0, 0);
         else if (valid) *(u32x4*)(a.y + (int64_t)m * N + nch) = v;
+        // PF: the stored value (after the residual, the mask and the rounding) back into the staged row
+        if constexpr (PF) *(u32x4*)(stg + row * ROWB + ch * 16) = valid ? v : u32x4{0u, 0u, 0u, 0u};
+      }
+      if constexpr (PF) {
+        // P += y_half^T a2_half: K = the half's 32 rows, one MFMA step per fragment
+        if (hf == 0) lds_barrier();  // every wave's part of the a2 image is written
+        else asm volatile("" ::: "memory");
+        // (lane map recomputed per half from an opaque copy: hoisted out of the tile loop, the 2 x K2/16 x 2
+        // swizzled addresses cost their count in VGPRs for the whole launch)
+        int ol = lane;
+        asm volatile("" : "+v"(ol));
+        const int g = ol >> 4, q4 = (ol >> 2) & 3, p4 = ol & 3;
+        const char* const a2 = smem + A2OFF;
+        bf16x8 ya[NI];
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+          ya[ni] = p_trfrag(stg + (8 * g + q4) * ROWB + (16 * ni + 4 * p4) * 2, stg + (8 * g + q4 + 4) * ROWB + (16 * ni + 4 * p4) * 2);
+        const int r1 = 32 * hf + 8 * g + q4, r2 = r1 + 4;
+        const int x1 = 2 * p_h<K2>(r1), x2 = 2 * p_h<K2>(r2);
+#pragma unroll
+        for (int nj = 0; nj < PNJ; ++nj) {
+          const int c = 2 * nj + (p4 >> 1), sub = (p4 & 1) * 8;
+          const bf16x8 bfr = p_trfrag(a2 + r1 * A2RB + ((c ^ x1) << 4) + sub, a2 + r2 * A2RB + ((c ^ x2) << 4) + sub);
+#pragma unroll
+          for (int ni = 0; ni < NI; ++ni)
+            pacc[ni][nj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ya[ni], bfr, pacc[ni][nj], 0, 0, 0);
+        }
       }
     }
+    // PF: this wave's reads of the a2 image done before the next tile's ring barrier lets it be rewritten
+    if constexpr (PF) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
   // statistics: reduce over the lanes holding the same channel chunk (lane = row * CPRW + ch),
   // one partial column per row group
@@ -406,6 +520,19 @@ __global__ __launch_bounds__(256, (K == 64 && EPI == PW_FWD) ? 3 : 2) void pw_st
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
+    }
+    if constexpr (PF) {
+      // the row group's slab [N][K2] (a row group without tiles stores zeros) and a fresh accumulator: lane
+      // (li, g) holds P[16 ni + 4 g + e][16 nj + li]
+      float* const slab = a.p_slab + (int64_t)col * N * K2;
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int nj = 0; nj < PNJ; ++nj) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) slab[(int64_t)(n0w + 16 * ni + 4 * g + e) * K2 + 16 * nj + li] = pacc[ni][nj][e];
+          pacc[ni][nj] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
     }
   };
   // Tile p of the block's stream landed.  In steady state NS-2 later tiles' DMAs and NS-1 tiles' stores
@@ -757,13 +884,13 @@ static int pw_wn(int K, int epi) {
 // Every block carries the same number of tiles, so the grid must be exactly the resident
 // capacity (blocks per CU from the occupancy API x CUs): a grid that lets the dispatcher put
 // 3 blocks on some CUs and 1 on others finishes at the pace of the fullest CU.
-template <int K, int WN, int NS, int EPI, bool DYN>
+template <int K, int WN, int NS, int EPI, bool DYN, int K2 = 0>
 static int pw_slots() {
   static int slots = [] {
     int dev = 0, cus = 0, per = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pw::pw_stream_kernel<K, WN, NS, EPI, DYN>, 256, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pw::pw_stream_kernel<K, WN, NS, EPI, DYN, K2>, 256, 0);
     return std::max(1, per) * std::max(1, cus);
   }();
   return slots;
@@ -788,8 +915,21 @@ static bool pw_dynamic() {
   return on;
 }
 
+// the fused-P variants of PW_DSUM (k2 columns of the second operand); 0: no such instantiation
+static bool pw_p_shape(int64_t K, int64_t k2) { return (K == 64 && k2 == 64) || (K == 128 && (k2 == 64 || k2 == 128)); }
 template <bool DYN>
-static int pw_cap(int64_t K, int epi) {
+static int pw_cap_p(int64_t K, int64_t k2) {
+  if (K == 64 && k2 == 64) return pw_slots<64, 32, 4, PW_DSUM, DYN, 64>();
+  if (K == 128 && k2 == 64) return pw_slots<128, 32, 3, PW_DSUM, DYN, 64>();
+  // (the dynamic <128, 32, 3> with 128 columns would spill 16 VGPRs: not instantiated -- pw_plan)
+  if constexpr (!DYN)
+    if (K == 128 && k2 == 128) return pw_slots<128, 32, 3, PW_DSUM, false, 128>();
+  return 0;
+}
+
+template <bool DYN>
+static int pw_cap(int64_t K, int epi, int64_t k2 = 0) {
+  if (k2 > 0) return pw_cap_p<DYN>(K, k2);
   return epi == PW_FWD ? pw_capacity<PW_FWD, DYN>((int)K)
                        : epi == PW_APPLY ? pw_capacity<PW_APPLY, DYN>((int)K)
                        : epi == PW_DSUM  ? pw_capacity<PW_DSUM, DYN>((int)K) : pw_capacity<PW_DGRAD, DYN>((int)K);
@@ -801,7 +941,8 @@ static int pw_cap(int64_t K, int epi) {
 // budget).  srg < rg (CU budget in force): the dynamic variant, rg = 8 srg row groups of >= 7 tiles each
 // (>= NS + 3: the stream claims the next row group NS + 2 tiles before the current one ends).
 struct PwPlan { int rg, srg; };
-static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi) {
+static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi, int64_t k2 = 0) {
+  if (k2 > 0 && (epi != PW_DSUM || !pw_p_shape(K, k2))) return {0, 0};
   if (K != 64 && K != 128 && K != 256) return {0, 0};
   if (epi != PW_FWD && epi != PW_DGRAD && epi != PW_APPLY && epi != PW_DSUM) return {0, 0};
   const int bnb = 4 * pw_wn((int)K, epi);
@@ -811,7 +952,10 @@ static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi) {
   const int64_t nbN = N / bnb;
   const int reserve = dpe_cu_reserve();
   if (reserve > 0 && pw_dynamic()) {
-    const int64_t srg = std::max<int64_t>(1, (pw_cap<true>(K, epi) - reserve) / nbN);
+    // fused P with 128 columns has no dynamic variant (registers): outside the envelope while a CU budget
+    // is in force -- the caller takes the separate weight grad
+    if (k2 == 128) return {0, 0};
+    const int64_t srg = std::max<int64_t>(1, (pw_cap<true>(K, epi, k2) - reserve) / nbN);
     // (an eighth static, the rest claimed: a block two or three times slower than its peers -- a
     // VALU-bound foreign wave on its SIMD -- ends its static row group well before the launch's end, and
     // the launch's tail is one short row group at its speed.  Worst-case hog probe, same box: 8 vs 3 row
@@ -821,16 +965,55 @@ static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi) {
     const int64_t rg = std::min<int64_t>(fac * srg, tiles / 7);
     if (rg > srg) return {(int)rg, (int)srg};
   }
-  int64_t rg = (pw_cap<false>(K, epi) - reserve) / nbN;
+  int64_t rg = (pw_cap<false>(K, epi, k2) - reserve) / nbN;
   rg = std::max<int64_t>(1, std::min<int64_t>(rg, tiles));
   return {(int)rg, (int)rg};
 }
 
 extern "C" int dpe_pw_rowgroups(int64_t M, int64_t N, int64_t K, int epi) { return pw_plan(M, N, K, epi).rg; }
 
+extern "C" int dpe_pw_p_rowgroups(int64_t M, int64_t N, int64_t K, int64_t k2) {
+  return k2 > 0 ? pw_plan(M, N, K, PW_DSUM, k2).rg : 0;
+}
+
+// P[i] = sum over row groups r (in order: 8 groups r = q, q + 8, ..., then the groups in order) of slab[r][i]
+__global__ __launch_bounds__(256) void pw_p_reduce_kernel(const float* __restrict__ slab, int rg, int64_t n,
+                                                          float* __restrict__ P) {
+  __shared__ float part[8][32];
+  const int o = threadIdx.x & 31, q = threadIdx.x >> 5;
+  const int64_t i = (int64_t)blockIdx.x * 32 + o;
+  float t = 0.f;
+  if (i < n) {
+    int r = q;
+    for (; r + 56 < rg; r += 64) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = slab[(int64_t)(r + 8 * k) * n + i];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t += v[k];
+    }
+    for (; r < rg; r += 8) t += slab[(int64_t)r * n + i];
+  }
+  part[q][o] = t;
+  __syncthreads();
+  if (q == 0 && i < n) {
+    float u = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u += part[k][o];
+    P[i] = u;
+  }
+}
+
+extern "C" int dpe_pw_p_reduce(const float* slab, int rg, int64_t n, float* P, hipStream_t st) {
+  if (rg <= 0 || n <= 0) return -1;
+  hipLaunchKernelGGL(pw_p_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, slab, rg, n, P);
+  return 0;
+}
+
 extern "C" int dpe_pw_launch(const PwArgs* args, int epi, hipStream_t st) {
   const PwArgs& a = *args;
-  if (a.rg <= 0 || a.rg != dpe_pw_rowgroups(a.M, a.N, a.K, epi)) return -1;
+  if (a.p_k2 < 0 || (a.p_k2 > 0 && (epi != PW_DSUM || !a.p_src || !a.p_slab))) return -1;
+  if (a.rg <= 0 || a.rg != pw_plan(a.M, a.N, a.K, epi, a.p_k2).rg) return -1;
   if (epi == PW_FWD && (a.residual || a.st_x)) return -1;
   if (a.st_x && !a.st_coef) return -1;
   if (epi == PW_DSUM && (a.st_x || !a.st_mask || !a.stats)) return -1;
@@ -839,7 +1022,7 @@ extern "C" int dpe_pw_launch(const PwArgs* args, int epi, hipStream_t st) {
     return -1;
   // resident row groups: all of them, or (CU budget in force) the first half, the rest claimed
   // (no claim counters -- a stream being captured: the static variant over all rg row groups)
-  const int srg = a.sched ? pw_plan(a.M, a.N, a.K, epi).srg : a.rg;
+  const int srg = a.sched ? pw_plan(a.M, a.N, a.K, epi, a.p_k2).srg : a.rg;
   const bool dyn = srg < a.rg;
   const int wn = pw_wn((int)a.K, epi);
   const dim3 grid((unsigned)(srg * (a.N / (4 * wn)))), block(256);
@@ -849,6 +1032,21 @@ extern "C" int dpe_pw_launch(const PwArgs* args, int epi, hipStream_t st) {
     else hipLaunchKernelGGL((pw::pw_stream_kernel<K_, WN_, NS_, E_, false>), grid, block, 0, st, a);       \
     return 0;                                                                                            \
   }
+#define PW_GO_P(K_, NS_, K2_)                                                                                \
+  if (a.K == K_ && a.p_k2 == K2_) {                                                                        \
+    if (dyn) hipLaunchKernelGGL((pw::pw_stream_kernel<K_, 32, NS_, PW_DSUM, true, K2_>), grid, block, 0, st, a);  \
+    else hipLaunchKernelGGL((pw::pw_stream_kernel<K_, 32, NS_, PW_DSUM, false, K2_>), grid, block, 0, st, a);     \
+    return 0;                                                                                              \
+  }
+  if (a.p_k2 > 0) {
+    PW_GO_P(64, 4, 64) PW_GO_P(128, 3, 64)
+    if (a.K == 128 && a.p_k2 == 128 && !dyn) {
+      hipLaunchKernelGGL((pw::pw_stream_kernel<128, 32, 3, PW_DSUM, false, 128>), grid, block, 0, st, a);
+      return 0;
+    }
+    return -1;
+  }
+#undef PW_GO_P
   PW_GO(64, 32, 4, PW_APPLY) PW_GO(128, 32, 3, PW_APPLY) PW_GO(256, 32, 2, PW_APPLY)
   PW_GO(64, 32, 4, PW_DSUM) PW_GO(128, 32, 3, PW_DSUM) PW_GO(256, 32, 2, PW_DSUM)
   PW_GO(64, DPE_PW64_DGRAD_WN, 4, PW_DGRAD) PW_GO(64, DPE_PW64_FWD_WN, 4, PW_FWD)

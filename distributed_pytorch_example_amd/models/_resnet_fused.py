@@ -130,6 +130,12 @@ _BND_GRAM = _GRAM and os.environ.get("DPE_BND_GRAM", "1") != "0"
 # concatenated-K data grad runs on the implicit GEMM's AX_CAT tiles at 301 us (28 % of its byte bound) and the
 # strided Gram pass + pilot cost 111 us (docs/perf_notes.md); kept as a tested building block.
 _BND_GRAM_S2 = _BND_GRAM and os.environ.get("DPE_BND_GRAM_S2", "0") == "1"
+# DPE_PW_FUSED_P=0: P = dz3^T a2 of the BN3 Gram backward by the deterministic weight grad over the stored dz3 (bit
+# for bit the calls before the fused form; A/B reference).  On: the next block's conv1 data grad, whose epilogue
+# stores dz3, forms P from the rows it holds (conv_dgrad_bn's p_src / p_coef, pwconv.hip) where
+# pw_dgrad_fused_p_ok holds -- bottleneck widths 64 / 128 behind a 64- or 128-wide conv1 (ResNet-50: layer1.0 to
+# layer1.2, layer2.1 and layer2.2).  Measurements: docs/perf_notes.md.
+_PW_FUSED_P = _GRAM and os.environ.get("DPE_PW_FUSED_P", "1") != "0"
 
 
 def _ax_ok(conv, cin) -> bool:
@@ -154,10 +160,13 @@ class _BN3Link:
     fused-epilogue result (BN3_i partials, identity of the masked dz3_i)
     handed back to block i's backward."""
 
-    __slots__ = ("h3", "coef", "mask", "part", "dz_ptr", "dz_shape", "pending", "gram")
+    __slots__ = ("h3", "coef", "mask", "part", "dz_ptr", "dz_shape", "pending", "gram", "psrc", "P")
 
     def __init__(self):
         self.h3 = self.coef = self.mask = self.part = None
+        # Gram path (DPE_PW_FUSED_P): block i's (a2 source, its BN2 coefficients or None), and P = dz3^T a2
+        # handed back beside part when block i+1's data grad formed it
+        self.psrc = self.P = None
         self.dz_ptr, self.dz_shape = 0, None
         self.gram = False  # block i ran BN3 by Gram algebra: block i+1's epilogue emits only the sum-dz partials
         # (h3, coef3, idn, idn_coef, out, bits): block i's output, allocated but not yet written --
@@ -306,6 +315,8 @@ class BottleneckFn(Function):
         if link_out is not None:
             link_out.h3, link_out.coef, link_out.mask = h3, c3, bits
             link_out.gram = gram is not None
+            if gram is not None and _PW_FUSED_P:
+                link_out.psrc = (h2, c2) if a2 is None else (a2, None)
             if gram is not None and block.down is not None and bnd is None:
                 # the next block's data-grad epilogue reduces the downsample BN's partials instead
                 # (sum dz, sum dz*(hd - mean_d)): row 0 serves BN3's Gram backward, both rows BN_d's
@@ -392,10 +403,13 @@ class BottleneckFn(Function):
             src, src_coef = (h2, c2) if a2 is None else (a2, None)
             w3 = convs[2].conv.weight
             s3, p3, d3 = _conv_conf(convs[2].conv)
-            P = torch.empty(w3.shape, dtype=torch.float32, device=w3.device)
-            # P = dz3^T a2 with its K splits summed in a fixed order: BN3's dgamma comes from it (overwrite:
-            # no zero fill of P)
-            C.conv_wgrad(dz3, src, P, s3, p3, d3, 1.0, src_coef, deterministic=True, overwrite=True)
+            P, lk.P, lk.psrc = lk.P, None, None
+            if P is None:
+                P = torch.empty(w3.shape, dtype=torch.float32, device=w3.device)
+                # P = dz3^T a2 with its K splits summed in a fixed order: BN3's dgamma comes from it (overwrite:
+                # no zero fill of P)
+                C.conv_wgrad(dz3, src, P, s3, p3, d3, 1.0, src_coef, deterministic=True, overwrite=True)
+            # (else: the next block's conv1 data grad formed P in the epilogue that stored dz3)
             bn, gb, gd, bb, bd = bn_sinks(2)
             wbuf, wdirect = grad_sink(w3)
             bcat, ebias = C.bn_gram_bwd(lk.part, P, ws[2], u3, sv, c3, bn.weight.detach(), M3, gb, bb, wbuf)
@@ -487,6 +501,17 @@ class BottleneckFn(Function):
                                            dgrad_bnb, dhd)
 
     @staticmethod
+    def _dgrad_sum(C, li, dh1, w, xshape, s, p, d, residual, res_mask, res_s2):
+        """conv1's data grad chained from a Gram-path block: stores that block's masked dz3 with the sum-dz
+        partials and, where the epilogue can (DPE_PW_FUSED_P), leaves P = dz3^T a2 in the link."""
+        src = li.psrc
+        if src is not None and C.pw_dgrad_fused_p_ok(xshape, w.shape[0], src[0].shape[-1]):
+            dx, part, li.P = C.conv_dgrad_bn(dh1, w, xshape, s, p, d, residual, None, None, None, res_mask, res_s2,
+                                             li.mask, p_src=src[0], p_coef=src[1])
+            return dx, part
+        return C.conv_dgrad_bn(dh1, w, xshape, s, p, d, residual, None, None, None, res_mask, res_s2, li.mask)
+
+    @staticmethod
     def _backward_tail(ctx, C, dz3, res_mask, dh2, grads, bn_sinks, bn_done, bn_bwd, wgrad, dgrad, dgrad_bnb, dhd=None,
                        down_done=False, dxd=None):
         """conv2 / conv1 / downsample gradients and dx, from dh2 (shared by the BN3 paths).  ``down_done``: the
@@ -517,8 +542,7 @@ class BottleneckFn(Function):
                 if li is None:
                     dx = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, None, None, None, None, True)[0]
                 elif li.gram and li.h3 is None:
-                    dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, None, None, None, None, True,
-                                               li.mask)
+                    dx, part = BottleneckFn._dgrad_sum(C, li, dh1, ws[0], list(x.shape), s, p, d, dxd, None, True)
                 else:
                     dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, li.h3, li.coef, li.mask, None,
                                                True)
@@ -534,8 +558,7 @@ class BottleneckFn(Function):
                 dxd = C.conv_dgrad(dhd, ws[3], [n, hh // 2, ww // 2, cin], [1, 1], [0, 0], [1, 1])  # compact
                 s, p, d = _conv_conf(convs[0].conv)
                 if li.gram and li.h3 is None:  # the previous block's BN3 runs by Gram algebra: only the sum-dz partials
-                    dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, None, None, None, None, True,
-                                               li.mask)
+                    dx, part = BottleneckFn._dgrad_sum(C, li, dh1, ws[0], list(x.shape), s, p, d, dxd, None, True)
                 else:
                     dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dxd, li.h3, li.coef, li.mask, None,
                                                True)
@@ -553,8 +576,7 @@ class BottleneckFn(Function):
                 li = ctx.link_in
                 s, p, d = _conv_conf(convs[0].conv)
                 if li.gram and li.h3 is None:  # (li.h3 set: the previous block's downsample BN input, reduced too)
-                    dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dz3, None, None, None, res_mask, False,
-                                               li.mask)
+                    dx, part = BottleneckFn._dgrad_sum(C, li, dh1, ws[0], list(x.shape), s, p, d, dz3, res_mask, False)
                 else:
                     dx, part = C.conv_dgrad_bn(dh1, ws[0], list(x.shape), s, p, d, dz3, li.h3, li.coef, li.mask, res_mask)
                 li.part, li.dz_ptr, li.dz_shape = part, dx.data_ptr(), tuple(dx.shape)
