@@ -149,22 +149,33 @@ Tensor nchw_to_s2d(const Tensor& x) {
   return y;
 }
 
-Tensor embedding_fwd(const Tensor& idx, const Tensor& wte, const c10::optional<Tensor>& wpe) {
+// an optional int32 GPU tensor of exactly n elements (position ids, document bounds); null when absent
+const int32_t* i32_opt(const c10::optional<Tensor>& t, int64_t n, const Tensor& like, const char* what) {
+  if (!has(t)) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->scalar_type() == at::kInt && t->is_contiguous() &&
+                  t->numel() == n, what, " must be a contiguous int32 tensor of ", n, " elements on the inputs' device");
+  return (const int32_t*)t->data_ptr();
+}
+
+Tensor embedding_fwd(const Tensor& idx, const Tensor& wte, const c10::optional<Tensor>& wpe,
+                     const c10::optional<Tensor>& pos) {
   CHECK_GPU(idx); CHECK_CONTIG(idx); CHECK_BF16(wte); CHECK_CONTIG(wte);
   TORCH_CHECK(idx.scalar_type() == at::kLong && idx.dim() == 2, "embedding: idx must be int64 [B,T]");
   const int64_t B = idx.size(0), T = idx.size(1), D = wte.size(1);
   Tensor out = at::empty({B, T, D}, wte.options().dtype(at::kFloat));
   const uint16_t* pe = has(wpe) ? bp(*wpe) : nullptr;
-  CHECK_RC(dpe_embedding_fwd((const int64_t*)idx.data_ptr(), bp(wte), pe, fp(out), B * T, (int)T, (int)D, cur_stream()),
+  CHECK_RC(dpe_embedding_fwd((const int64_t*)idx.data_ptr(), bp(wte), pe, fp(out), B * T, (int)T, (int)D,
+                             i32_opt(pos, B * T, idx, "embedding: pos"), cur_stream()),
            "embedding_fwd");
   return out;
 }
 
-void embedding_bwd(const Tensor& idx, const Tensor& dout, Tensor& dwte, const c10::optional<Tensor>& dwpe) {
+void embedding_bwd(const Tensor& idx, const Tensor& dout, Tensor& dwte, const c10::optional<Tensor>& dwpe,
+                   const c10::optional<Tensor>& pos) {
   CHECK_GPU(dout); CHECK_F32(dout); CHECK_CONTIG(dout); CHECK_F32(dwte);
   const int64_t B = idx.size(0), T = idx.size(1), D = dwte.size(1);
   CHECK_RC(dpe_embedding_bwd((const int64_t*)idx.data_ptr(), fp(dout), fp(dwte), fpom(dwpe), B * T, (int)T, (int)D,
-                             cur_stream()), "embedding_bwd");
+                             i32_opt(pos, B * T, idx, "embedding: pos"), cur_stream()), "embedding_bwd");
 }
 
 // --------------------------------------------------------------- optimizer
@@ -370,9 +381,11 @@ void layernorm_bwd_finalize_group(const std::vector<Tensor>& parts, const std::v
 }
 
 // ---------------------------------------------------------------- attention
-// qkv: [B, T, 3, H, D] bf16 -> out [B, T, H, D] bf16, lse [B, H, T] f32 (both optionally caller-allocated)
+// qkv: [B, T, 3, H, D] bf16 -> out [B, T, H, D] bf16, lse [B, H, T] f32 (both optionally caller-allocated).
+// doc_start / doc_end (int32 [B, T], together): the packed-document mask doc_start[b, i] <= j <= i.
 std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal, const c10::optional<Tensor>& out_,
-                             const c10::optional<Tensor>& lse_) {
+                             const c10::optional<Tensor>& lse_, const c10::optional<Tensor>& doc_start,
+                             const c10::optional<Tensor>& doc_end) {
   CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_CONTIG(qkv);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   TORCH_CHECK(qkv.numel() == B * T * 3 * H * D, "attn: qkv must be [B,T,3,H,D]");
@@ -381,21 +394,27 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool ca
   Tensor lse = has(lse_) ? *lse_ : at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
   CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out); CHECK_GPU(lse); CHECK_F32(lse); CHECK_CONTIG(lse);
   TORCH_CHECK(out.numel() == B * T * H * D && lse.numel() == B * H * T, "attn_fwd: out is [B,T,H,D], lse [B,H,T]");
-  CHECK_RC(dpe_attn_fwd(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal, cur_stream()),
+  TORCH_CHECK(has(doc_start) == has(doc_end), "attn_fwd: doc_start and doc_end go together");
+  CHECK_RC(dpe_attn_fwd(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal,
+                        i32_opt(doc_start, B * T, qkv, "attn_fwd: doc_start"),
+                        i32_opt(doc_end, B * T, qkv, "attn_fwd: doc_end"), cur_stream()),
            "attn_fwd");
   return {out, lse};
 }
 
 Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const Tensor& lse, int64_t H, double scale,
-                bool causal, const c10::optional<Tensor>& dqkv_) {
+                bool causal, const c10::optional<Tensor>& dqkv_, const c10::optional<Tensor>& doc_start,
+                const c10::optional<Tensor>& doc_end) {
   CHECK_GPU(qkv); CHECK_BF16(dout); CHECK_CONTIG(dout); CHECK_CONTIG(out);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   Tensor dqkv = has(dqkv_) ? *dqkv_ : at::empty_like(qkv);
   CHECK_GPU(dqkv); CHECK_BF16(dqkv); CHECK_CONTIG(dqkv);
   TORCH_CHECK(dqkv.numel() == qkv.numel(), "attn_bwd: dqkv must have qkv's size");
   Tensor delta = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
+  TORCH_CHECK(has(doc_start) == has(doc_end), "attn_bwd: doc_start and doc_end go together");
   CHECK_RC(dpe_attn_bwd(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), nullptr, bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
-                        (float)scale, causal, cur_stream()), "attn_bwd");
+                        (float)scale, causal, i32_opt(doc_start, B * T, qkv, "attn_bwd: doc_start"),
+                        i32_opt(doc_end, B * T, qkv, "attn_bwd: doc_end"), cur_stream()), "attn_bwd");
   return dqkv;
 }
 
@@ -417,8 +436,10 @@ void register_ops(pybind11::module& m) {
   m.def("colsum", &colsum, py::arg("dy"), py::arg("db"), py::arg("accumulate") = false);
   m.def("nchw_to_s2d", &nchw_to_s2d, py::arg("x"));
   m.def("nchw_to_nhwc", &nchw_to_nhwc, py::arg("x"), py::arg("cpad") = 8);
-  m.def("embedding_fwd", &embedding_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe") = py::none());
-  m.def("embedding_bwd", &embedding_bwd, py::arg("idx"), py::arg("dout"), py::arg("dwte"), py::arg("dwpe") = py::none());
+  m.def("embedding_fwd", &embedding_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe") = py::none(),
+        py::arg("pos") = py::none());
+  m.def("embedding_bwd", &embedding_bwd, py::arg("idx"), py::arg("dout"), py::arg("dwte"), py::arg("dwpe") = py::none(),
+        py::arg("pos") = py::none());
   m.def("optim_step", &optim_step);
   m.def("optim_grad_norm", &optim_grad_norm, py::arg("desc"), py::arg("chunks"), py::arg("partials"), py::arg("out"),
         py::arg("max_norm"), py::arg("hp") = py::none(), py::arg("skip_nonfinite") = false);
@@ -461,9 +482,11 @@ void register_ops(pybind11::module& m) {
           CHECK_RC(dpe_hog_stop((unsigned*)stop.data_ptr(), (unsigned)v, cur_stream()), "hog_stop");
         }, py::arg("stop"), py::arg("value") = 1, "set a cu_hog stop flag, ordered on the current stream");
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("causal") = true,
-        py::arg("out") = py::none(), py::arg("lse") = py::none());
+        py::arg("out") = py::none(), py::arg("lse") = py::none(), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("H"),
-        py::arg("scale"), py::arg("causal") = true, py::arg("dqkv") = py::none());
+        py::arg("scale"), py::arg("causal") = true, py::arg("dqkv") = py::none(), py::arg("doc_start") = py::none(),
+        py::arg("doc_end") = py::none());
   m.def("set_attn_staged", [](bool on) { return dpe_set_attn_staged(on ? 1 : 0) != 0; }, py::arg("on"),
         "attention on the register-staged kernels instead of the LDS-DMA ones (test switch; default off); returns the "
         "previous setting");

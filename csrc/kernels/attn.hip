@@ -33,6 +33,8 @@
 //   from -delta, so dS = P*(dP - delta) is one multiply.  Two
 //   extra MFMA passes replace fp32 dQ atomics across key tiles (the chip's
 //   ~1.3 TB/s atomic rate: ~210 MB per layer).
+// Packed documents (doc_start / doc_end, block-diagonal causal mask): PACKED instantiations of the three LDS-DMA
+//   kernels, described at each; the causal instantiations compile to what they were without the template.
 #include <type_traits>
 
 #include "common.h"
@@ -310,9 +312,19 @@ DPE_DEVICE void attn_vm_drain() {
   asm volatile("" ::: "memory");
 }
 
+//
+// PACKED (documents packed end to end into a row, block-diagonal causal mask): doc_start[b][t] is the row index of
+// the first token of t's document (non-decreasing, <= t), and query i sees key j iff doc_start[b][i] <= j <= i.
+// The workgroup starts at the key tile that holds its first query's document start, a wave skips the tiles that
+// end before its own first query's, and a tile that crosses a document start of the wave takes a third compute
+// path with both bounds.  In that path a tile can be fully masked for some rows of a wave while their running
+// max is still -inf (the causal kernel never meets this: key 0 is visible to every query), so a masked element is
+// never given a score: it is left out of the row max and its P is an exact 0 by select, whatever m is.  Values of
+// doc_start only choose tiles (clamped to the causal kernel's walk) and masks, never an address.
+template <bool PACKED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_fwd_dma_kernel(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse2, int B, int T, int H,
-    float sl2) {
+    float sl2, const int* __restrict__ doc_start) {
   constexpr int KB = 2 * AKV * 64, STG = KB + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
@@ -326,6 +338,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
   const bool live = q0w < T;
   const int ktw = live ? (q0w + 31) / AKV : -1;
   const int nkt = min((qt * FQ + FQ - 1) / AKV, T / AKV - 1) + 1;
+  // packed: first key tile of the workgroup / of the wave, first key no lower mask is needed from, the lane's bounds
+  int kt0 = 0, klo = 0, dshi = 0, ds[2] = {0, 0};
+  if constexpr (PACKED) {
+    const int* dsb = doc_start + (int64_t)b * T;
+    kt0 = min(max(__builtin_amdgcn_readfirstlane(dsb[qt * FQ]) / AKV, 0), nkt - 1);
+    if (live) {
+      klo = __builtin_amdgcn_readfirstlane(dsb[q0w]) / AKV;
+      dshi = __builtin_amdgcn_readfirstlane(dsb[q0w + 31]);
+      ds[0] = dsb[q0w + li];
+      ds[1] = dsb[q0w + 16 + li];
+    }
+  }
 
   bf16x8 qf[2][2];
 #pragma unroll
@@ -374,8 +398,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
   const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});
   const int kd = (q0w + 1) / AKV;
 
-  auto compute = [&](int kt, const char* s, auto maskc) {
-    constexpr bool MASK = decltype(maskc)::value;
+  // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask
+  auto compute = [&](int kt, const char* s, auto maskc) __attribute__((always_inline)) {
+    constexpr int MK = decltype(maskc)::value;
+    constexpr bool MASK = MK == 1;
     f32x4 sc[2][4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
@@ -395,18 +421,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
           for (int e = 0; e < 4; ++e)
             if (16 * nt + e > lim) sc[r][nt][e] = -INFINITY;
       }
-      float mx = sc[r][0][0];
+      float mx;
+      if constexpr (MK == 2) {  // the row max over the visible keys only; -inf for a row that sees none here
+        const int lim = q0w + 16 * r + li - kt * AKV - 4 * g, lo = ds[r] - kt * AKV - 4 * g;
+        mx = -INFINITY;
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
+        for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int e = (nt == 0); e < 4; ++e) mx = fmaxf(mx, sc[r][nt][e]);
-      mc[r] = rowmax4(mx) * sl2;
-      need[r] = mc[r] > m[r] + RESCALE_TH;
+          for (int e = 0; e < 4; ++e) mx = ((16 * nt + e <= lim) & (16 * nt + e >= lo)) ? fmaxf(mx, sc[r][nt][e]) : mx;
+        mx = rowmax4(mx);
+        mc[r] = mx == -INFINITY ? mx : mx * sl2;
+        need[r] = mc[r] > (m[r] == -INFINITY ? m[r] : m[r] + RESCALE_TH);  // false for a row without a visible key
+      } else {
+        mx = sc[r][0][0];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int e = (nt == 0); e < 4; ++e) mx = fmaxf(mx, sc[r][nt][e]);
+        mc[r] = rowmax4(mx) * sl2;
+        need[r] = mc[r] > m[r] + RESCALE_TH;
+      }
     }
     if (__builtin_amdgcn_ballot_w64(need[0] || need[1])) {
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
-        const float alpha = need[r] ? __builtin_amdgcn_exp2f(m[r] - mc[r]) : 1.f;
+        float alpha;
+        if constexpr (MK == 2)  // a first visible key: the accumulators are still 0, nothing to rescale
+          alpha = (need[r] & (m[r] != -INFINITY)) ? __builtin_amdgcn_exp2f(m[r] - mc[r]) : 1.f;
+        else
+          alpha = need[r] ? __builtin_amdgcn_exp2f(m[r] - mc[r]) : 1.f;
         m[r] = need[r] ? mc[r] : m[r];
         accl[r] *= alpha;
 #pragma unroll
@@ -416,11 +459,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
     bf16x8 pk[2][2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-      const float nm = -m[r];
+      if constexpr (MK == 2) {  // a masked P is 0 by select after the exp2 (which may have overflowed), m = -inf or not
+        const float nm = m[r] == -INFINITY ? 0.f : -m[r];
+        const int lim = q0w + 16 * r + li - kt * AKV - 4 * g, lo = ds[r] - kt * AKV - 4 * g;
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
+        for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) sc[r][nt][e] = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
+          for (int e = 0; e < 4; ++e) {
+            const float pv = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
+            sc[r][nt][e] = ((16 * nt + e <= lim) & (16 * nt + e >= lo)) ? pv : 0.f;
+          }
+      } else {
+        const float nm = -m[r];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sc[r][nt][e] = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
+      }
       pk[r][0] = pack_frag(sc[r][0], sc[r][1]);
       pk[r][1] = pack_frag(sc[r][2], sc[r][3]);
       accl[r] = MFMA(ones, pk[r][1], MFMA(ones, pk[r][0], accl[r]));
@@ -433,7 +488,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
     }
   };
 
-  dma_tile(0, smem);
+  dma_tile(kt0, smem);
   attn_vm_drain();
   __syncthreads();
   // the tile loop unrolled by two: each step's LDS buffer is a compile-time constant
@@ -441,12 +496,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
     constexpr int cur = decltype(bufc)::value;
     const bool more = kt + 1 < nkt;
     if (more) dma_tile(kt + 1, smem + (cur ^ 1) * STG);  // read last in step kt - 1, before its barrier
-    if (kt < kd) compute(kt, smem + cur * STG, std::false_type{});
-    else if (kt <= ktw) compute(kt, smem + cur * STG, std::true_type{});
+    if constexpr (PACKED) {
+      if (kt >= klo && kt <= ktw) {
+        if (kt * AKV < dshi) compute(kt, smem + cur * STG, std::integral_constant<int, 2>{});
+        else if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
+        else compute(kt, smem + cur * STG, std::integral_constant<int, 1>{});
+      }
+    } else {
+      if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
+      else if (kt <= ktw) compute(kt, smem + cur * STG, std::integral_constant<int, 1>{});
+    }
     if (more) attn_vm_drain();
     __syncthreads();
   };
-  for (int kt = 0; kt < nkt; kt += 2) {
+  for (int kt = kt0; kt < nkt; kt += 2) {
     step(kt, std::integral_constant<int, 0>{});
     if (kt + 1 < nkt) step(kt + 1, std::integral_constant<int, 1>{});
   }
@@ -640,12 +703,19 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
 // global -> LDS by LDS-DMA one tile ahead (no staging registers, no ds_write_b128 per image: 8 of
 // them per thread and tile in attn_bwd_kernel); lse / -delta still go through registers (128 floats).
 // Each lane fetches the chunk the swizzled image places at its slot (the swizzles are involutions).
+// PACKED: the query-tile loop ends at the tile that holds the last query of the workgroup's last key's document
+// (doc_end - 1; per wave, of the wave's last key's), and a tile whose last query's document starts behind the wave's
+// first key masks on both bounds.  The tile's 64 doc_start values are staged beside lse / -delta (+256 B per
+// buffer); P of a masked query is 0 by select after the exp2, so an overflowed exp2 of a foreign document's score
+// never reaches dS.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
                                                        const float* __restrict__ lse2, const float* __restrict__ delta,
                                                        uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
-                                                       float scale) {
-  // per buffer: Qk Qm dOk dOm (8 KB each) + lse, delta (512 B)
-  constexpr int BUF = 4 * 8192 + 512;
+                                                       float scale, const int* __restrict__ doc_start,
+                                                       const int* __restrict__ doc_end) {
+  // per buffer: Qk Qm dOk dOm (8 KB each) + lse, delta (512 B) (+ packed: doc_start, 256 B)
+  constexpr int BUF = 4 * 8192 + 512 + (PACKED ? 256 : 0);
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
   const int nqt = T / AQ, BH = B * H;
@@ -673,6 +743,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
     }
   // Q / dO of a query tile: LDS-DMA into [Qk | Qm | Ok | Om] (8 KiB each); lse / -delta via registers
   float lv = 0.f;
+  [[maybe_unused]] int dsv = 0;
   const float* pl = (tid < 64 ? lse2 + tid : delta + (tid - 64)) + (int64_t)bh * T;
   const __amdgpu_buffer_rsrc_t rq =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(qb), (short)0, (int)(T * RS * 2), 0x00020000);
@@ -699,11 +770,23 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
 #pragma unroll
     for (int i = 0; i < 8; ++i) attn_dma16(i < 4 ? rq : rdo, base + (w + 4 * i) * 1024, voff[i], i < 4 ? sq : so);
     if (tid < 128) lv = pl[qt * AQ];
+    if constexpr (PACKED)
+      if (tid >= 128 && tid < 192) dsv = doc_start[(int64_t)b * T + qt * AQ + (tid - 128)];
   };
   auto stash = [&](int buf) {  // after the tile's DMA has landed (attn_vm_drain)
     if (tid < 128) ((float*)(smem + buf * BUF + 4 * 8192))[tid] = tid < 64 ? lv : -lv;  // [0,64) lse, [64,128) -delta
+    if constexpr (PACKED)
+      if (tid >= 128 && tid < 192) ((int*)(smem + buf * BUF + 4 * 8192 + 512))[tid - 128] = dsv;
   };
   const int qs = (kt * BKW) / AQ;
+  // packed: the exclusive end of the workgroup's query-tile loop (clamped into the causal walk) and the wave's last tile
+  int qend = nqt, qhiw = nqt;
+  if constexpr (PACKED) {
+    const int* deb = doc_end + (int64_t)b * T;
+    const int ew = __builtin_amdgcn_readfirstlane(deb[min(kt * BKW + BKW - 1, T - 1)]);
+    qend = min(max((max(ew, 1) - 1) / AQ + 1, qs + 1), nqt);
+    if (live) qhiw = (max(__builtin_amdgcn_readfirstlane(deb[k0w + 31]), 1) - 1) / AQ;
+  }
   dma_tile(qs, 0);
   attn_vm_drain();
   stash(0);
@@ -718,10 +801,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
   // fragment address is a hoisted per-lane offset plus an immediate
   auto step = [&](int qt, auto bufc) {
     constexpr int cur = decltype(bufc)::value;
-    const bool more = qt + 1 < nqt;
+    const bool more = qt + 1 < qend;
     if (more) dma_tile(qt + 1, cur ^ 1);  // in flight during this tile's MFMAs (cur ^ 1 last read before the previous barrier)
-    auto compute = [&](const char* base, auto maskc) {
-      constexpr bool MASK = decltype(maskc)::value;
+    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask
+    auto compute = [&](const char* base, auto maskc) __attribute__((always_inline)) {
+      constexpr int MK = decltype(maskc)::value;
+      constexpr bool MASK = MK == 1;
       const char* Qk = base;
       const char* Qm = base + 8192;
       const char* Ok = base + 2 * 8192;
@@ -745,6 +830,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
         const f32x4 l4 = *(const f32x4*)(sl + 16 * mt + 4 * g);
+        [[maybe_unused]] u32x4 d4;
+        if constexpr (MK == 2) d4 = *(const u32x4*)(base + 4 * 8192 + 512 + 4 * (16 * mt + 4 * g));
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -752,6 +839,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
             float p = __builtin_amdgcn_exp2f(fmaf(ps[r][mt][e], sl2, -l4[e]));
             if constexpr (MASK)
               if (k0w + 16 * r + li > qt * AQ + 16 * mt + 4 * g + e) p = 0.f;
+            if constexpr (MK == 2) {  // the key is behind the query, or the query's document starts behind the key
+              const int key = k0w + 16 * r + li;
+              p = ((key > qt * AQ + 16 * mt + 4 * g + e) | ((int)d4[e] > key)) ? 0.f : p;
+            }
             ps[r][mt][e] = p;                        // P
             dp[r][mt][e] = p * dp[r][mt][e];  // dS (unscaled)
           }
@@ -775,9 +866,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
       }
     };
     // query tiles whose first query is past the wave's last key need no causal mask
-    if (live && qt >= qtw) {
-      if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::false_type{});
-      else compute(smem + cur * BUF, std::true_type{});
+    if constexpr (PACKED) {
+      if (live && qt >= qtw && qt <= qhiw) {
+        // doc_start is monotone: the tile's last query has the largest
+        const int dlast = __builtin_amdgcn_readfirstlane(((const int*)(smem + cur * BUF + 4 * 8192 + 512))[AQ - 1]);
+        if (dlast > k0w) compute(smem + cur * BUF, std::integral_constant<int, 2>{});
+        else if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
+        else compute(smem + cur * BUF, std::integral_constant<int, 1>{});
+      }
+    } else if (live && qt >= qtw) {
+      if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
+      else compute(smem + cur * BUF, std::integral_constant<int, 1>{});
     }
     if (more) {
       attn_vm_drain();
@@ -785,9 +884,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
     }
     __syncthreads();
   };
-  for (int qt = qs; qt < nqt; qt += 2) {
+  for (int qt = qs; qt < qend; qt += 2) {
     step(qt, std::integral_constant<int, 0>{});
-    if (qt + 1 < nqt) step(qt + 1, std::integral_constant<int, 1>{});
+    if (qt + 1 < qend) step(qt + 1, std::integral_constant<int, 1>{});
   }
   if (!live) return;
   // dK, dV (bf16) -> dqkv[b, key, 1|2, h, :]
@@ -956,11 +1055,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const uint16_t* __rest
 #ifndef ATTN_DQ_WAVES
 #define ATTN_DQ_WAVES 2
 #endif
+// PACKED: the forward's tile walk (attn_fwd_dma_kernel) -- the workgroup starts at its first query's document, a
+// wave skips the tiles before its own, and a tile that crosses a document start of the wave masks on both bounds;
+// P of a masked key is 0 by select after the exp2, as for the causal mask.
+template <bool PACKED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAVES))) void attn_bwd_dq_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o,
                                                           const uint16_t* __restrict__ dout,
                                                           const float* __restrict__ lse2, float* __restrict__ delta,
                                                           uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
-                                                          float scale) {
+                                                          float scale, const int* __restrict__ doc_start) {
   // per buffer: K (two d-halves, K-contig) 8K | V (same) 8K | K permuted-row image 8K
   constexpr int KI = 0, VI = 2 * AKV * 64, KP = 4 * AKV * 64, STG = KP + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
@@ -1005,6 +1108,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
     ndl[r] = -dot;
   }
 
+  // packed: first key tile of the workgroup / of the wave, first key no lower mask is needed from, the lane's bounds
+  int kt0 = 0, klo = 0, dshi = 0, ds[2] = {0, 0};
+  if constexpr (PACKED) {
+    const int* dsb = doc_start + (int64_t)b * T;
+    kt0 = min(max(__builtin_amdgcn_readfirstlane(dsb[qt * FQ]) / AKV, 0), nkt - 1);
+    if (live) {
+      klo = __builtin_amdgcn_readfirstlane(dsb[q0w]) / AKV;
+      dshi = __builtin_amdgcn_readfirstlane(dsb[q0w + 31]);
+      ds[0] = dsb[q0w + li];
+      ds[1] = dsb[q0w + 16 + li];
+    }
+  }
+
   // the sequence's qkv rows from K of head h on: one buffer resource, tile advance in soffset
   const __amdgpu_buffer_rsrc_t rkv =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(kb), (short)0, (int)(T * RS * 2), 0x00020000);
@@ -1035,7 +1151,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
   for (int r = 0; r < 2; ++r)
 #pragma unroll
     for (int d = 0; d < 4; ++d) acc[r][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  dma_tile(0, 0);
+  dma_tile(kt0, 0);
   attn_vm_drain();
   __syncthreads();
   // the tile loop unrolled by two: the LDS buffer of each step is a compile-time constant, so every
@@ -1044,8 +1160,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
     constexpr int cur = decltype(bufc)::value;
     const bool more = kt + 1 < nkt;
     if (more) dma_tile(kt + 1, cur ^ 1);  // cur ^ 1 last read before the previous barrier
-    auto compute = [&](const char* s, auto maskc) {
-      constexpr bool MASK = decltype(maskc)::value;
+    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask
+    auto compute = [&](const char* s, auto maskc) __attribute__((always_inline)) {
+      constexpr int MK = decltype(maskc)::value;
+      constexpr bool MASK = MK == 1;
       f32x4 sc[2][4], dp[2][4];
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
@@ -1068,6 +1186,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
             float p = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, -lq[r]));
             if constexpr (MASK)
               if (kt * AKV + 16 * nt + 4 * g + e > myq) p = 0.f;
+            if constexpr (MK == 2) {
+              const int key = kt * AKV + 16 * nt + 4 * g + e;
+              p = ((key > myq) | (key < ds[r])) ? 0.f : p;
+            }
             dp[r][nt][e] = p * dp[r][nt][e];  // dS^T (unscaled); dP^T started from -delta
           }
         dd[r][0] = pack_frag(dp[r][0], dp[r][1]);
@@ -1080,12 +1202,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
         for (int r = 0; r < 2; ++r) acc[r][d] = MFMA(a1, dd[r][1], MFMA(a0, dd[r][0], acc[r][d]));
       }
     };
-    if (kt < kd) compute(smem + cur * STG, std::false_type{});
-    else if (kt <= ktw) compute(smem + cur * STG, std::true_type{});
+    if constexpr (PACKED) {
+      if (kt >= klo && kt <= ktw) {
+        if (kt * AKV < dshi) compute(smem + cur * STG, std::integral_constant<int, 2>{});
+        else if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
+        else compute(smem + cur * STG, std::integral_constant<int, 1>{});
+      }
+    } else {
+      if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
+      else if (kt <= ktw) compute(smem + cur * STG, std::integral_constant<int, 1>{});
+    }
     if (more) attn_vm_drain();
     __syncthreads();
   };
-  for (int kt = 0; kt < nkt; kt += 2) {
+  for (int kt = kt0; kt < nkt; kt += 2) {
     step(kt, std::integral_constant<int, 0>{});
     if (kt + 1 < nkt) step(kt + 1, std::integral_constant<int, 1>{});
   }
@@ -1116,49 +1246,61 @@ extern "C" int dpe_set_attn_staged(int on) {
   return was;
 }
 
+// doc_start / doc_end (both or neither; int32 [B, T]): the packed-document mask, LDS-DMA kernels only.
 extern "C" int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int causal,
-                            hipStream_t st) {
+                            const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
   if (D != AD || T % AKV != 0 || !causal) return -1;
   const float sl2 = scale * 1.4426950408889634f;
-#ifdef DPE_ATTN_FWD_STAGED
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
-#else
   // one sequence's qkv rows must fit the DMA kernel's 32-bit buffer range
-  if (!g_attn_staged && (int64_t)T * 3 * H * AD * 2 < (1LL << 31))
-    hipLaunchKernelGGL(attn_fwd_dma_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, lse, B, T, H,
-                       sl2);
+  const bool dma = !g_attn_staged && (int64_t)T * 3 * H * AD * 2 < (1LL << 31);
+  const dim3 grid(B * H * ((T + FQ - 1) / FQ));
+  if (doc_start) {
+    if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
+    hipLaunchKernelGGL(attn_fwd_dma_kernel<true>, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start);
+    return 0;
+  }
+#ifdef DPE_ATTN_FWD_STAGED
+  hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
+#else
+  if (dma)
+    hipLaunchKernelGGL(attn_fwd_dma_kernel<false>, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, (const int*)nullptr);
   else
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
+    hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
 #endif
   return 0;
 }
 
 extern "C" int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                             float* dq_acc, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal,
-                            hipStream_t st) {
+                            const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
   (void)dq_acc;  // dQ is not accumulated with atomics (attn_bwd_dq_kernel)
   if (D != AD || T % AKV != 0 || !causal) return -1;
   const float sl2 = scale * 1.4426950408889634f;
   // one sequence's qkv / dO rows must fit the DMA kernels' 32-bit buffer ranges
   const bool dma = !g_attn_staged && (int64_t)T * 3 * H * AD * 2 < (1LL << 31);
+  const dim3 gq(B * H * ((T + FQ - 1) / FQ)), gk(B * H * ((T + BKW - 1) / BKW));
   // dQ first: it also writes delta = rowsum(dO * O), which the dK/dV kernel reads
+  if (doc_start) {
+    if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
+    hipLaunchKernelGGL(attn_bwd_dq_dma_kernel<true>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2,
+                       scale, doc_start);
+    hipLaunchKernelGGL(attn_bwd_dma_kernel<true>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
+                       doc_start, doc_end);
+    return 0;
+  }
 #ifdef DPE_ATTN_BWD_STAGED
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse, delta,
-                     dqkv, B, T, H, sl2, scale);
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * H * ((T + BKW - 1) / BKW)), dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B,
-                     T, H, sl2, scale);
+  hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2, scale);
+  hipLaunchKernelGGL(attn_bwd_kernel, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale);
   (void)dma;
 #else
   if (dma) {
-    hipLaunchKernelGGL(attn_bwd_dq_dma_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse,
-                       delta, dqkv, B, T, H, sl2, scale);
-    hipLaunchKernelGGL(attn_bwd_dma_kernel, dim3(B * H * ((T + BKW - 1) / BKW)), dim3(256), 0, st, qkv, dout, lse, delta,
-                       dqkv, B, T, H, sl2, scale);
+    hipLaunchKernelGGL(attn_bwd_dq_dma_kernel<false>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2,
+                       scale, (const int*)nullptr);
+    hipLaunchKernelGGL(attn_bwd_dma_kernel<false>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
+                       (const int*)nullptr, (const int*)nullptr);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out, dout, lse, delta,
-                       dqkv, B, T, H, sl2, scale);
-    hipLaunchKernelGGL(attn_bwd_kernel, dim3(B * H * ((T + BKW - 1) / BKW)), dim3(256), 0, st, qkv, dout, lse, delta, dqkv,
-                       B, T, H, sl2, scale);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2, scale);
+    hipLaunchKernelGGL(attn_bwd_kernel, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale);
   }
 #endif
   return 0;

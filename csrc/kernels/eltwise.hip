@@ -287,10 +287,10 @@ __global__ __launch_bounds__(256) void conv_w_flipT_multi_kernel(const FlipDesc*
 }
 
 // ----------------------------------------------------------- embedding
-// out[r][:] = wte[idx[r]][:] (+ wpe[r % T][:]) ; D % 8 == 0, weights bf16, out f32
+// out[r][:] = wte[idx[r]][:] (+ wpe[pos ? pos[r] : r % T][:]) ; D % 8 == 0, weights bf16, out f32
 __global__ __launch_bounds__(ET) void embedding_fwd_kernel(const int64_t* __restrict__ idx, const uint16_t* __restrict__ wte,
                                                            const uint16_t* __restrict__ wpe, float* __restrict__ out,
-                                                           int64_t rows, int T, int D) {
+                                                           int64_t rows, int T, int D, const int32_t* __restrict__ pos) {
   const int CPR = D / 8;
   GRID_STRIDE(i, rows * CPR) {
     const int64_t r = i / CPR;
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(ET) void embedding_fwd_kernel(const int64_t* __rest
     unpack8(*(const u32x4*)(wte + idx[r] * D + c8), a);
     if (wpe) {
       float b[8];
-      unpack8(*(const u32x4*)(wpe + (r % T) * D + c8), b);
+      unpack8(*(const u32x4*)(wpe + (pos ? (int64_t)pos[r] : r % T) * D + c8), b);
 #pragma unroll
       for (int e = 0; e < 8; ++e) a[e] += b[e];
     }
@@ -308,16 +308,16 @@ __global__ __launch_bounds__(ET) void embedding_fwd_kernel(const int64_t* __rest
   }
 }
 
-// dwte[idx[r]] += dout[r]; dwpe[r % T] += dout[r]   (fp32 atomics, 256-B wave segments)
+// dwte[idx[r]] += dout[r]; dwpe[pos ? pos[r] : r % T] += dout[r]   (fp32 atomics, 256-B wave segments)
 __global__ __launch_bounds__(ET) void embedding_bwd_kernel(const int64_t* __restrict__ idx, const float* __restrict__ dout,
                                                            float* __restrict__ dwte, float* __restrict__ dwpe, int64_t rows,
-                                                           int T, int D) {
+                                                           int T, int D, const int32_t* __restrict__ pos) {
   GRID_STRIDE(i, rows * D) {
     const int64_t r = i / D;
     const int d = (int)(i % D);
     const float g = dout[i];
     atomicAdd(dwte + idx[r] * D + d, g);
-    if (dwpe) atomicAdd(dwpe + (r % T) * D + d, g);
+    if (dwpe) atomicAdd(dwpe + (pos ? (int64_t)pos[r] : r % T) * D + d, g);
   }
 }
 
@@ -415,14 +415,14 @@ extern "C" int dpe_nchw_to_nhwc(const float* x, uint16_t* y, int N, int C, int H
   return 0;
 }
 extern "C" int dpe_embedding_fwd(const int64_t* idx, const uint16_t* wte, const uint16_t* wpe, float* out, int64_t rows, int T,
-                                 int D, hipStream_t st) {
+                                 int D, const int32_t* pos, hipStream_t st) {
   if (D % 8) return -1;
-  hipLaunchKernelGGL(embedding_fwd_kernel, dim3(egrid(rows * D / 8)), dim3(ET), 0, st, idx, wte, wpe, out, rows, T, D);
+  hipLaunchKernelGGL(embedding_fwd_kernel, dim3(egrid(rows * D / 8)), dim3(ET), 0, st, idx, wte, wpe, out, rows, T, D, pos);
   return 0;
 }
 extern "C" int dpe_embedding_bwd(const int64_t* idx, const float* dout, float* dwte, float* dwpe, int64_t rows, int T, int D,
-                                 hipStream_t st) {
-  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(egrid(rows * D)), dim3(ET), 0, st, idx, dout, dwte, dwpe, rows, T, D);
+                                 const int32_t* pos, hipStream_t st) {
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(egrid(rows * D)), dim3(ET), 0, st, idx, dout, dwte, dwpe, rows, T, D, pos);
   return 0;
 }
 

@@ -97,10 +97,11 @@ int dpe_conv_w_flipT(const uint16_t* w, uint16_t* wt, int K, int R, int S, int C
 int dpe_flip_desc_bytes();
 int dpe_flip_blocks(int K, int C, int Rp, int Sp);
 int dpe_conv_w_flipT_multi(const void* desc, const int* start, int n, int total_blocks, hipStream_t st);
+// pos: position id per row (int32 [rows]); null = r % T
 int dpe_embedding_fwd(const int64_t* idx, const uint16_t* wte, const uint16_t* wpe, float* out, int64_t rows, int T, int D,
-                      hipStream_t st);
+                      const int32_t* pos, hipStream_t st);
 int dpe_embedding_bwd(const int64_t* idx, const float* dout, float* dwte, float* dwpe, int64_t rows, int T, int D,
-                      hipStream_t st);
+                      const int32_t* pos, hipStream_t st);
 int64_t dpe_cu_hog_buf_floats(int nblocks);
 int dpe_cu_hog(int nblocks, int threads, int lds_bytes, double us, int vgprs, const unsigned* stop, float* sink,
                int sleepy, float* buf, hipStream_t st);
@@ -132,10 +133,12 @@ int dpe_layernorm_bwd(const uint16_t* dy, const void* x, int x_bf16, const float
 int dpe_layernorm_bwd_finalize_group(const float* const* parts, const int64_t* rows, const int* Ds, float* const* dws,
                                      float* const* dbs, int n, hipStream_t st);
 // ---- attn.hip
+// doc_start / doc_end: the packed-document mask (int32 [B, T], both or neither; null = plain causal)
 int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int causal,
-                 hipStream_t st);
+                 const int32_t* doc_start, const int32_t* doc_end, hipStream_t st);
 int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                 float* dq_acc, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, hipStream_t st);
+                 float* dq_acc, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, const int32_t* doc_start,
+                 const int32_t* doc_end, hipStream_t st);
 int dpe_set_attn_staged(int on);
 // ---- gemm_f32.hip
 int dpe_gemm_f32(const float* A, const float* B, float* C, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,

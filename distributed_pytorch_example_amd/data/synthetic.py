@@ -53,10 +53,16 @@ class SyntheticDataset(Dataset):
 
 
 class SyntheticTokens(Dataset):
-    """Token sequences for GPT-style models: ``(x[t], y[t]) = (tok[t], tok[t+1])``."""
+    """Token sequences for GPT-style models: ``(x[t], y[t]) = (tok[t], tok[t+1])``.
+
+    ``doc_len_mean``: every row is short documents packed end to end.  Their lengths are geometric with that
+    mean (minimum 1, drawn after the tokens from the same seeded generator, so the tokens do not depend on the
+    option); ``doc_start`` [N, seq_len] int32 holds, per token, the index in the row of its document's first
+    token (ops.functional.doc_bounds), and a target whose token belongs to the next document is -100, the
+    cross-entropy kernels' ignore_index.  Items are then ``(x, y, doc_start)``."""
 
     def __init__(self, num_samples: int, seq_len: int, vocab_size: int, seed: Optional[int] = None,
-                 device: torch.device | str = "cpu") -> None:
+                 device: torch.device | str = "cpu", doc_len_mean: Optional[float] = None) -> None:
         g = None
         if seed is not None:
             g = torch.Generator(device="cpu")
@@ -65,12 +71,30 @@ class SyntheticTokens(Dataset):
         self.tokens = toks.to(device)
         self.num_samples = num_samples
         self.seq_len = seq_len
+        self.doc_start = None
+        self.targets = None
+        if doc_len_mean is not None:
+            if not doc_len_mean >= 1:
+                raise ValueError("doc_len_mean must be >= 1")
+            # geometric lengths with minimum 1 <=> every token after a row's first starts a document with
+            # probability 1 / mean, independently
+            first = torch.rand((num_samples, seq_len + 1), generator=g) < 1.0 / doc_len_mean
+            first[:, 0] = True
+            first[:, seq_len] = False  # the token behind the row continues its last document
+            t = torch.arange(seq_len + 1).expand(num_samples, -1)
+            ds = torch.cummax(torch.where(first, t, torch.zeros_like(t)), dim=1).values
+            tgt = toks[:, 1:].clone()
+            tgt[first[:, 1:]] = -100  # the next token opens another document
+            self.doc_start = ds[:, :-1].to(torch.int32).contiguous().to(device)
+            self.targets = tgt.to(device)
 
     def __len__(self) -> int:
         return self.num_samples
 
     def __getitem__(self, idx):
         t = self.tokens[idx]
+        if self.doc_start is not None:
+            return t[..., :-1], self.targets[idx], self.doc_start[idx]
         return t[..., :-1], t[..., 1:]
 
 
@@ -83,9 +107,12 @@ class DeviceLoader:
         self.batch_size = batch_size
         self.sampler = sampler
         self.drop_last = drop_last
+        self._tgt = self._ds = None
         if isinstance(dataset, SyntheticTokens):
             self._x = dataset.tokens
             self._y = None
+            if dataset.doc_start is not None:  # packed documents: batches are (x, y, doc_start)
+                self._tgt, self._ds = dataset.targets, dataset.doc_start
         else:
             self._x = dataset.data
             self._y = dataset.labels
@@ -94,6 +121,8 @@ class DeviceLoader:
             self._x = self._x.to(device=dev, dtype=dtype if (dtype is not None and self._x.is_floating_point()) else None)
             if self._y is not None:
                 self._y = self._y.to(dev)
+        if self._ds is not None and self._ds.device != dev:
+            self._tgt, self._ds = self._tgt.to(dev), self._ds.to(dev)
         self.device = dev
 
     def __len__(self) -> int:
@@ -115,7 +144,9 @@ class DeviceLoader:
         nb = len(self)
         for b in range(nb):
             sl = idx[b * self.batch_size: min(n, (b + 1) * self.batch_size)]
-            if self._y is None:
+            if self._ds is not None:
+                yield self._x.index_select(0, sl)[:, :-1], self._tgt.index_select(0, sl), self._ds.index_select(0, sl)
+            elif self._y is None:
                 t = self._x.index_select(0, sl)
                 yield t[:, :-1], t[:, 1:]
             else:

@@ -187,7 +187,7 @@ def block_params(blk):
 
 class BlockFn(Function):
     @staticmethod
-    def forward(ctx, x, blk, *params):
+    def forward(ctx, x, blk, doc, *params):
         C = ext()
         B, T, D = x.shape
         H = blk.n_head
@@ -201,7 +201,10 @@ class BlockFn(Function):
         h1, m1, r1 = C.layernorm_fwd(x, blk.ln_1.weight.detach(), opt(blk.ln_1.bias), blk.ln_1.eps)
         qkv = C.linear_fwd(h1, shadow(blk.c_attn.weight), opt(blk.c_attn.bias), 0, False, None, None)
         qkv5 = qkv.view(B, T, 3, H, hd)
-        a, lse = C.attn_fwd(qkv5, H, scale, True)
+        if doc is None:
+            a, lse = C.attn_fwd(qkv5, H, scale, True)
+        else:  # packed documents: (doc_start, doc_end, pos) of Fx.doc_bounds
+            a, lse = C.attn_fwd(qkv5, H, scale, True, doc_start=doc[0], doc_end=doc[1])
         a = a.view(B, T, D)
         x2 = C.linear_fwd(a, shadow(blk.attn_proj.weight), opt(blk.attn_proj.bias), 0, True, x, None)
         h2, m2, r2 = C.layernorm_fwd(x2, blk.ln_2.weight.detach(), opt(blk.ln_2.bias), blk.ln_2.eps)
@@ -210,7 +213,7 @@ class BlockFn(Function):
         u = C.linear_fwd(h2, shadow(blk.c_fc.weight), opt(blk.c_fc.bias), 2, False, None, None, v)
         y = C.linear_fwd(u, shadow(blk.mlp_proj.weight), opt(blk.mlp_proj.bias), 0, True, x2, None)
         ctx.save_for_backward(x, h1, m1, r1, qkv5, a, lse, x2, h2, m2, r2, v, u)
-        ctx.blk, ctx.scale = blk, scale
+        ctx.blk, ctx.scale, ctx.doc = blk, scale, doc
         for p in params:
             note_use(p)
         return y
@@ -283,8 +286,11 @@ class BlockFn(Function):
         dh2 = linear_bwd(blk.c_fc, dv, h2)
         g2, g2b = ln_bwd(blk.ln_2, dh2, x2, m2, r2, g)
         da = linear_bwd(blk.attn_proj, g2b, a)
-        dqkv = C.attn_bwd(qkv5, a.view(qkv5.shape[0], qkv5.shape[1], qkv5.shape[3], qkv5.shape[4]), da, lse,
-                          blk.n_head, ctx.scale, True)
+        a4 = a.view(qkv5.shape[0], qkv5.shape[1], qkv5.shape[3], qkv5.shape[4])
+        if ctx.doc is None:
+            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True)
+        else:
+            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True, doc_start=ctx.doc[0], doc_end=ctx.doc[1])
         dqkv = dqkv.view(a.shape[0], a.shape[1], -1)
         dh1 = linear_bwd(blk.c_attn, dqkv, h1)
         g1, g1b = ln_bwd(blk.ln_1, dh1, x, m1, r1, g2)
@@ -296,9 +302,9 @@ class BlockFn(Function):
             flush_wgrad_queue()  # every _WG_GROUP layers, and always at the first block (end of backward)
         _carry[0] = (g1, g1b, g1._version)
         pgrads = [grads.get(id(p)) for p in block_params(blk)]
-        return (g1, None, *pgrads)
+        return (g1, None, None, *pgrads)
 
 
-def block_forward(blk, x):
-    return BlockFn.apply(x, blk, *block_params(blk))
+def block_forward(blk, x, doc=None):
+    return BlockFn.apply(x, blk, doc, *block_params(blk))
 

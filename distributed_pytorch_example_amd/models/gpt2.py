@@ -63,16 +63,17 @@ class Block(nn.Module):
         for lin in (self.c_attn, self.attn_proj, self.c_fc, self.mlp_proj):
             lin.weight._dpe_overwrite_ok = True
 
-    def forward(self, x):
+    def forward(self, x, doc=None):
+        """``doc``: the (doc_start, doc_end, pos) of Fx.doc_bounds for packed documents, None for one per row."""
         # (the fused block calls the attention kernels directly: only for the shapes they take)
         if (x.is_cuda and self.fused and torch.is_grad_enabled()
                 and Fx.attn_kernel_ok(x.shape[1], x.shape[2] // self.n_head)):
             from ._gpt2_fused import block_forward  # hand-scheduled fwd/bwd, one autograd node
 
-            return block_forward(self, x)
+            return block_forward(self, x, doc)
         h = self.ln_1(x)
         qkv = self.c_attn(h)
-        a = Fx.causal_attention(qkv, self.n_head)
+        a = Fx.causal_attention(qkv, self.n_head) if doc is None else Fx.causal_attention(qkv, self.n_head, doc)
         x = Fx.linear_residual(a, self.attn_proj.weight, self.attn_proj.bias, x)
         h = self.ln_2(x)
         u = Fx.gelu(self.c_fc(h))
@@ -110,19 +111,27 @@ class GPT2(nn.Module):
                     if lin.bias is not None:
                         lin.bias.zero_()
 
-    def forward(self, idx, targets=None):
+    def forward(self, idx, targets=None, doc_start=None):
         """Logits [B, T, V(p)], or -- with ``targets`` -- the mean next-token
         cross-entropy through the fused LM-head + CE op (logits never materialise
-        outside it)."""
+        outside it).  ``doc_start`` [B, T] (see Fx.doc_bounds): the rows hold packed documents; attention
+        stays inside each and positions restart at its first token."""
         B, T = idx.shape
         assert T <= self.cfg.block_size, "sequence longer than block_size"
         if _FUSED and idx.is_cuda:
             from ._gpt2_fused import reset_wgrad_queue
 
             reset_wgrad_queue()
-        x = Fx.embedding(idx, self.wte, self.wpe[:T] if not idx.is_cuda else self.wpe)
-        for blk in self.h:
-            x = blk(x)
+        if doc_start is None:
+            x = Fx.embedding(idx, self.wte, self.wpe[:T] if not idx.is_cuda else self.wpe)
+            for blk in self.h:
+                x = blk(x)
+        else:
+            assert doc_start.shape == idx.shape, "doc_start must have idx's shape"
+            doc = Fx.doc_bounds(doc_start)  # once per batch, shared by every layer
+            x = Fx.embedding(idx, self.wte, self.wpe, doc[2])
+            for blk in self.h:
+                x = blk(x, doc)
         x = self.ln_f(x)
         if targets is not None:
             return Fx.lm_head_ce(x, self.wte, targets)

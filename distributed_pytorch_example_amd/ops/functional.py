@@ -600,10 +600,10 @@ def layer_norm(x, weight, bias=None, eps: float = 1e-5):
 # ================================================================ Embedding
 class _EmbFn(Function):
     @staticmethod
-    def forward(ctx, idx, wte, wpe, wte16, wpe16):
-        out = ext().embedding_fwd(idx, wte16, wpe16)
+    def forward(ctx, idx, wte, wpe, wte16, wpe16, pos=None):
+        out = ext().embedding_fwd(idx, wte16, wpe16, pos)
         ctx.save_for_backward(idx)
-        ctx.wte, ctx.wpe = wte, wpe
+        ctx.wte, ctx.wpe, ctx.pos = wte, wpe, pos
         note_use(wte)
         if wpe is not None:
             note_use(wpe)
@@ -617,38 +617,108 @@ class _EmbFn(Function):
         for p, buf, d in ((ctx.wte, tb, td), (ctx.wpe, pb, pd)):  # the scatter-add needs a zeroed start
             if p is not None and d and grad_fresh(p):
                 buf.zero_()
-        ext().embedding_bwd(idx, dout.contiguous().float(), tb, pb)
+        ext().embedding_bwd(idx, dout.contiguous().float(), tb, pb, ctx.pos)
         grad_done(ctx.wte, td)
         if ctx.wpe is not None:
             grad_done(ctx.wpe, pd)
-        return None, (None if td else tb), (None if (pd or ctx.wpe is None) else pb), None, None
+        return None, (None if td else tb), (None if (pd or ctx.wpe is None) else pb), None, None, None
 
 
-def embedding(idx, wte, wpe=None):
-    """tok + pos embedding -> f32 [B,T,D] residual stream."""
+def embedding(idx, wte, wpe=None, pos=None):
+    """tok + pos embedding -> f32 [B,T,D] residual stream.  ``pos`` (int32 [B, T], from doc_bounds): the position
+    id of every token in place of its index in the row."""
     if not idx.is_cuda:
         T = idx.shape[1]
         x = F.embedding(idx, wte)
         if wpe is not None:
-            x = x + wpe[:T].unsqueeze(0)
+            x = x + (wpe[:T].unsqueeze(0) if pos is None else F.embedding(pos.long(), wpe))
         return x
-    return _EmbFn.apply(idx, wte, wpe, shadow(wte), shadow(wpe) if wpe is not None else None)
+    return _EmbFn.apply(idx, wte, wpe, shadow(wte), shadow(wpe) if wpe is not None else None,
+                        pos.to(torch.int32).contiguous() if pos is not None else None)
 
 
 # ================================================================ Attention
+# ---- packed documents: several documents end to end in one row, block-diagonal causal mask.
+# doc_start [B, T]: the index within the row of the first token of token t's document.  Valid iff
+# doc_start[b, 0] == 0 and doc_start[b, t] is doc_start[b, t - 1] or t.  Query i sees key j iff
+# doc_start[b, i] <= j <= i; token t's position id is t - doc_start[b, t]; all zeros = plain causal attention.
+def doc_bounds(doc_start):
+    """doc_start [B, T] (any integer dtype) -> (doc_start, doc_end, pos), int32 [B, T] each: doc_end is the
+    exclusive end of the token's document, pos its position id.  Device ops only, no host sync (graph-safe);
+    call it once per batch and hand the result to every layer."""
+    ds = doc_start.to(torch.int32).contiguous()
+    T = ds.shape[-1]
+    t = torch.arange(T, device=ds.device, dtype=torch.int32).expand_as(ds)
+    # the next document start at or after t + 1: a reverse running minimum over "t where a document starts, else T"
+    nxt = torch.where(ds == t, t, torch.full_like(t, T))
+    nxt = torch.cat([nxt[..., 1:], torch.full_like(nxt[..., :1], T)], dim=-1)
+    de = torch.flip(torch.cummin(torch.flip(nxt, (-1,)), dim=-1).values, (-1,)).to(torch.int32).contiguous()
+    # (clamped: an invalid doc_start may give wrong numbers, never a position outside the table)
+    return ds, de, (t - ds).clamp_(0, T - 1).contiguous()
+
+
+def doc_start_from_lengths(lengths, T: int):
+    """Document lengths of one row (a sequence of positive ints; the last one is cut at, or extended to, T) ->
+    doc_start int32 [T]."""
+    out = torch.zeros(T, dtype=torch.int32)
+    s = 0
+    for n in lengths:
+        n = int(n)
+        if n < 1:
+            raise ValueError("document lengths must be at least 1")
+        if s >= T:
+            break
+        out[s:] = s
+        s += n
+    return out
+
+
+def doc_start_from_eos(idx, eos_id: int):
+    """idx [B, T] -> doc_start int32 [B, T]: the token after an EOS starts a document.  Device ops, no sync."""
+    T = idx.shape[-1]
+    t = torch.arange(T, device=idx.device, dtype=torch.int32).expand(idx.shape)
+    first = torch.ones_like(idx, dtype=torch.bool)
+    first[..., 1:] = idx[..., :-1] == eos_id
+    return torch.cummax(torch.where(first, t, torch.zeros_like(t)), dim=-1).values.to(torch.int32)
+
+
+def check_doc_start(doc_start) -> None:
+    """Raise ValueError unless doc_start [B, T] is valid (see above).  Synchronises: opt-in, outside the step."""
+    if doc_start.dim() != 2:
+        raise ValueError("doc_start must be [B, T]")
+    ds = doc_start.long()
+    t = torch.arange(ds.shape[1], device=ds.device).expand_as(ds)
+    if bool((ds[:, 0] != 0).any()):
+        raise ValueError("doc_start[:, 0] must be 0")
+    if bool((ds > t).any()) or bool((ds < 0).any()):
+        raise ValueError("doc_start[b, t] must lie in [0, t]")
+    if bool((ds[:, 1:] < ds[:, :-1]).any()):
+        raise ValueError("doc_start must be non-decreasing")
+    if bool(((ds[:, 1:] != ds[:, :-1]) & (ds[:, 1:] != t[:, 1:])).any()):
+        raise ValueError("doc_start[b, t] must be doc_start[b, t - 1] or t")
+
+
 class _AttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, H: int, scale: float):
-        out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True)
+    def forward(ctx, qkv, H: int, scale: float, doc_start=None, doc_end=None):
+        if doc_start is None:
+            out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True)
+        else:
+            out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True, doc_start=doc_start, doc_end=doc_end)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.H, ctx.scale = H, scale
+        ctx.H, ctx.scale, ctx.doc = H, scale, (doc_start, doc_end)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True)
-        return dqkv, None, None
+        ds, de = ctx.doc
+        if ds is None:
+            dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True)
+        else:
+            dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True,
+                                  doc_start=ds, doc_end=de)
+        return dqkv, None, None, None, None
 
 
 def attn_kernel_ok(T: int, D: int) -> bool:
@@ -656,29 +726,40 @@ def attn_kernel_ok(T: int, D: int) -> bool:
     return D == 64 and T % 64 == 0
 
 
-def _causal_attention_torch(qkv5, scale: float):
-    """Shapes outside the kernels' range: explicit masked softmax(Q K^T) V in fp32 torch ops (autograd
-    differentiates it), result in qkv's dtype like the kernel's."""
+def _causal_attention_torch(qkv5, scale: float, doc_start=None):
+    """Shapes outside the kernels' range (and every packed-document call off the GPU): explicit masked
+    softmax(Q K^T) V in fp32 torch ops (autograd differentiates it), result in qkv's dtype like the kernel's.
+    ``doc_start`` [B, T]: keys before the query's document are masked too."""
     q, k, v = qkv5.float().permute(2, 0, 3, 1, 4)  # each [B, H, T, D]
     T = q.shape[-2]
     s = (q @ k.transpose(-1, -2)) * scale
     s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+    if doc_start is not None:
+        j = torch.arange(T, device=s.device)
+        s = s.masked_fill((j[None, None, :] < doc_start.long()[:, :, None]).unsqueeze(1), float("-inf"))
     o = torch.softmax(s, dim=-1) @ v
     return o.transpose(1, 2).to(qkv5.dtype)  # [B, T, H, D]
 
 
-def causal_attention(qkv, n_head: int):
-    """qkv: [B, T, 3*H*D] -> [B, T, H*D] causal softmax attention."""
+def causal_attention(qkv, n_head: int, doc_bounds=None):
+    """qkv: [B, T, 3*H*D] -> [B, T, H*D] causal softmax attention.  ``doc_bounds`` (the tuple doc_bounds()
+    returns): attention stays inside each packed document."""
     B, T, three_hd = qkv.shape
     D = three_hd // (3 * n_head)
     scale = 1.0 / math.sqrt(D)
+    if doc_bounds is not None:
+        ds, de = doc_bounds[0], doc_bounds[1]
+        if not qkv.is_cuda or not attn_kernel_ok(T, D):
+            return _causal_attention_torch(qkv.reshape(B, T, 3, n_head, D), scale, ds).reshape(B, T, n_head * D)
+        out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, ds, de)
+        return out.reshape(B, T, n_head * D)
     if not qkv.is_cuda:
         q, k, v = qkv.float().view(B, T, 3, n_head, D).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return o.transpose(1, 2).reshape(B, T, n_head * D)
     if not attn_kernel_ok(T, D):
         return _causal_attention_torch(qkv.reshape(B, T, 3, n_head, D), scale).reshape(B, T, n_head * D)
-    out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale)
+    out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, None, None)
     return out.reshape(B, T, n_head * D)
 
 

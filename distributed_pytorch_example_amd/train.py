@@ -70,6 +70,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loader", default="auto", choices=["auto", "device", "torch"])
     p.add_argument("--image-size", type=int, default=224)
     p.add_argument("--seq-len", type=int, default=1024)
+    p.add_argument("--doc-len-mean", type=float, default=None,
+                   help="gpt2 models: pack documents of this mean length (geometric) into every row; attention stays "
+                        "inside a document, positions restart, targets across a boundary are ignored")
     p.add_argument("--max-steps", type=int, default=None, help="stop each epoch after this many steps")
     p.add_argument("--async-checkpoint", action="store_true")
     p.add_argument("--auto-resume", action="store_true", help="resume from <checkpoint-dir>/latest_model.pt if present")
@@ -99,8 +102,9 @@ def _datasets(args, device):
         va = SyntheticDataset(max(1, args.num_samples // 10), shp, ncls, seed=None if args.seed is None else args.seed + 1)
         return tr, va, ncls
     vocab = 50257 if args.model == "gpt2" else 512
-    tr = SyntheticTokens(args.num_samples, args.seq_len, vocab, seed=args.seed)
-    va = SyntheticTokens(max(1, args.num_samples // 10), args.seq_len, vocab, seed=None if args.seed is None else args.seed + 1)
+    tr = SyntheticTokens(args.num_samples, args.seq_len, vocab, seed=args.seed, doc_len_mean=args.doc_len_mean)
+    va = SyntheticTokens(max(1, args.num_samples // 10), args.seq_len, vocab, seed=None if args.seed is None else args.seed + 1,
+                         doc_len_mean=args.doc_len_mean)
     return tr, va, vocab
 
 
@@ -116,17 +120,18 @@ def train_epoch(model, loader, optimizer, criterion, device, epoch, rank, grad_a
     # the epoch's last micro-batch always syncs and steps, also when --max-steps cuts the epoch
     # short: leftover no_sync gradients must not leak into the next epoch's first update
     n_eff = min(nb, max_steps) if max_steps is not None else nb
-    for batch_idx, (data, target) in enumerate(loader):
+    for batch_idx, (data, target, *doc) in enumerate(loader):  # doc: [doc_start] of a packed-document dataset
         if max_steps is not None and batch_idx >= max_steps:
             break
         fault.maybe_inject(epoch, batch_idx)
         data, target = data.to(device, non_blocking=True), target.to(device, non_blocking=True)
+        doc = [d.to(device, non_blocking=True) for d in doc]
         sync = (batch_idx + 1) % grad_accum == 0 or batch_idx + 1 == n_eff
         ctx = model.no_sync() if (not sync and hasattr(model, "no_sync")) else _null()
         with ctx:
             with tracing.range("forward"):
                 if fused_loss:
-                    loss = model(data, target)
+                    loss = model(data, target, *doc)
                 else:
                     output = model(data)
                     loss = criterion(output, target)
@@ -153,11 +158,11 @@ def validate(model, loader, criterion, device, num_classes, max_steps=None, watc
     correct = torch.zeros((), dtype=torch.float64, device=device)
     total = 0
     nbatches = 0
-    for i, (data, target) in enumerate(loader):
+    for i, (data, target, *doc) in enumerate(loader):
         if max_steps is not None and i >= max_steps:
             break
         data, target = data.to(device), target.to(device)
-        output = model(data)
+        output = model(data, None, doc[0].to(device)) if doc else model(data)
         s, c = Fx.cross_entropy_eval(output, target, num_classes)
         total_loss += s / target.numel()
         correct += c
@@ -185,6 +190,10 @@ def main(argv=None):
         parser.error("--skip-nonfinite-steps needs --clip-grad-norm")
     if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
         parser.error("--clip-grad-norm must be > 0")
+    if args.doc_len_mean is not None and not args.model.startswith("gpt2"):
+        parser.error("--doc-len-mean needs a gpt2 model")
+    if args.doc_len_mean is not None and not args.doc_len_mean >= 1:
+        parser.error("--doc-len-mean must be >= 1")
     if args.trust_coefficient is not None and args.optimizer not in ("lars", "lamb"):
         parser.error("--trust-coefficient needs --optimizer lars or lamb")
     ensure_single_process_env()
