@@ -40,14 +40,17 @@ std::vector<Tensor> cross_entropy(const Tensor& logits, const Tensor& labels, in
 // Training form: (out4 = [loss_sum, correct, mean over non-ignored rows, 1 / their count], dlogits).  The
 // mean and the backward scale come out of the reduction kernel itself (no torch count / clamp / divide
 // launches at the forward -> backward seam).
+// label_smoothing / z_loss (both 0: the plain kernels): see csrc/kernels/loss.hip.
 std::vector<Tensor> cross_entropy_mean(const Tensor& logits, const Tensor& labels, int64_t V, bool grad_bf16,
-                                       int64_t ignore_index, bool inplace) {
+                                       int64_t ignore_index, bool inplace, double label_smoothing, double z_loss) {
   CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_CONTIG(labels);
   TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
   const bool in_bf16 = logits.scalar_type() == at::kBFloat16;
   TORCH_CHECK(in_bf16 || logits.scalar_type() == at::kFloat, "logits must be f32 or bf16");
   const int64_t ld = logits.size(-1), B = logits.numel() / ld;
   TORCH_CHECK(labels.numel() == B, "labels size mismatch");
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "cross_entropy_mean: label_smoothing must be in [0, 1)");
+  TORCH_CHECK(z_loss >= 0.0, "cross_entropy_mean: z_loss must be >= 0");
   auto fo = logits.options().dtype(at::kFloat);
   Tensor rows = at::empty({B}, fo);
   Tensor out4 = at::zeros({4}, fo);
@@ -58,9 +61,17 @@ std::vector<Tensor> cross_entropy_mean(const Tensor& logits, const Tensor& label
   } else {
     d = at::empty(logits.sizes(), logits.options().dtype(grad_bf16 ? at::kBFloat16 : at::kFloat));
   }
-  CHECK_RC(dpe_cross_entropy_mean(logits.data_ptr(), in_bf16, (const int64_t*)labels.data_ptr(), (int)B, (int)V, ld, 1.f,
-                                  d.data_ptr(), grad_bf16, fp(rows), fp(out4), (int)ignore_index, cur_stream()),
-           "cross_entropy_mean");
+  if (label_smoothing == 0.0 && z_loss == 0.0) {
+    CHECK_RC(dpe_cross_entropy_mean(logits.data_ptr(), in_bf16, (const int64_t*)labels.data_ptr(), (int)B, (int)V, ld, 1.f,
+                                    d.data_ptr(), grad_bf16, fp(rows), fp(out4), (int)ignore_index, cur_stream()),
+             "cross_entropy_mean");
+  } else {
+    TORCH_CHECK(V > 0 && V <= ld, "cross_entropy_mean: V must be in [1, row length]");
+    CHECK_RC(dpe_cross_entropy_mean_reg(logits.data_ptr(), in_bf16, (const int64_t*)labels.data_ptr(), (int)B, (int)V, ld, 1.f,
+                                        d.data_ptr(), grad_bf16, fp(rows), fp(out4), (int)ignore_index,
+                                        (float)label_smoothing, (float)z_loss, cur_stream()),
+             "cross_entropy_mean");
+  }
   return {out4, d};
 }
 
@@ -235,6 +246,20 @@ void optim_clip_coef(const Tensor& partials, int64_t nchunks, Tensor& out, const
   CHECK_RC(dpe_optim_clip_coef(fp(partials), (int)nchunks, fp(out), fp(max_norm), fp(hp), (int)(hp.numel() / 12),
                                skip_nonfinite ? 1 : 0, cur_stream()),
            "optim_clip_coef");
+}
+
+// The scheduled lr of this step into every group's hp row and `cur`; the device counter sched[0] advances by
+// the step's ok flag.  sched: fp64 [optim_sched_header() + n_groups] (csrc/kernels/optim.hip).
+void optim_lr_schedule(Tensor& hp, Tensor& sched, Tensor& cur) {
+  CHECK_GPU(hp); CHECK_F32(hp); CHECK_CONTIG(hp);
+  CHECK_GPU(sched); CHECK_CONTIG(sched);
+  CHECK_GPU(cur); CHECK_F32(cur); CHECK_CONTIG(cur);
+  TORCH_CHECK(sched.scalar_type() == at::kDouble, "optim_lr_schedule: sched is fp64");
+  TORCH_CHECK(hp.numel() > 0 && hp.numel() % 12 == 0, "optim_lr_schedule: hp holds 12 floats per group");
+  const int64_t ng = hp.numel() / 12;
+  TORCH_CHECK(sched.numel() == dpe_optim_sched_header() + ng, "optim_lr_schedule: sched holds the header and one base lr per group");
+  TORCH_CHECK(cur.numel() == ng, "optim_lr_schedule: cur holds one lr per group");
+  CHECK_RC(dpe_optim_lr_schedule(fp(hp), (int)ng, (double*)sched.data_ptr(), fp(cur), cur_stream()), "optim_lr_schedule");
 }
 
 // LARS / LAMB (kind 0 / 1): the table checks of the other entry points plus the sizes of what the trust
@@ -423,8 +448,9 @@ Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const 
 void register_ops(pybind11::module& m) {
   namespace py = pybind11;
   m.def("cross_entropy_mean", &cross_entropy_mean, py::arg("logits"), py::arg("labels"), py::arg("V"),
-        py::arg("grad_bf16"), py::arg("ignore_index") = -100, py::arg("inplace") = false,
-        "training CE: (out4 = [sum, correct, mean, 1/n_valid], softmax - onehot)");
+        py::arg("grad_bf16"), py::arg("ignore_index") = -100, py::arg("inplace") = false, py::arg("label_smoothing") = 0.0,
+        py::arg("z_loss") = 0.0,
+        "training CE: (out4 = [sum, correct, mean, 1/n_valid], d loss_row / d logits), optionally label-smoothed / with z-loss");
   m.def("ce_grad_scale", &ce_grad_scale, py::arg("d"), py::arg("g"), py::arg("inv_n"), "d * g * inv_n (device scalars)");
   m.def("cross_entropy", &cross_entropy, py::arg("logits"), py::arg("labels"), py::arg("V"), py::arg("grad_scale"),
         py::arg("want_grad"), py::arg("grad_bf16"), py::arg("ignore_index") = -100, py::arg("inplace") = false);
@@ -446,6 +472,8 @@ void register_ops(pybind11::module& m) {
   m.def("optim_grad_scale", &optim_grad_scale, py::arg("desc"), py::arg("chunks"), py::arg("out"));
   m.def("optim_clip_coef", &optim_clip_coef, py::arg("partials"), py::arg("nchunks"), py::arg("out"), py::arg("max_norm"),
         py::arg("hp"), py::arg("skip_nonfinite") = false);
+  m.def("optim_lr_schedule", &optim_lr_schedule, py::arg("hp"), py::arg("sched"), py::arg("cur"));
+  m.def("optim_sched_header", []() { return dpe_optim_sched_header(); });
   m.def("optim_trust_partials", &optim_trust_partials);
   m.def("optim_trust_ratio", &optim_trust_ratio);
   m.def("optim_trust_step", &optim_trust_step);

@@ -82,6 +82,10 @@ int dpe_cross_entropy(const void* logits, int in_bf16, const int64_t* labels, in
 int dpe_cross_entropy_mean(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
                            float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* out4, int ignore_index,
                            hipStream_t st);
+// label smoothing eps in [0, 1) and z-loss weight zl >= 0 (the REG instantiations of the CE kernels)
+int dpe_cross_entropy_mean_reg(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
+                               float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* out4,
+                               int ignore_index, float eps, float zl, hipStream_t st);
 int dpe_ce_grad_scale(const void* d, void* o, int64_t n, int bf16, const float* g, const float* inv_n, hipStream_t st);
 // ---- eltwise.hip
 int dpe_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t st);
@@ -116,6 +120,8 @@ int dpe_optim_grad_norm(const void* desc, const void* chunks, int nchunks, float
 int dpe_optim_grad_scale(const void* desc, const void* chunks, int nchunks, const float* out, hipStream_t st);
 int dpe_optim_clip_coef(const float* partials, int nchunks, float* out, const float* max_norm, float* hp, int ngroups, int skip,
                         hipStream_t st);
+int dpe_optim_sched_header();  // doubles in the schedule block before the per-group base lrs
+int dpe_optim_lr_schedule(float* hp, int ngroups, double* sched, float* cur, hipStream_t st);
 int dpe_optim_trust_partials(int kind, const void* desc, const void* chunks, int nchunks, const float* hp, const float* steps,
                              float* part_w, float* part_x, hipStream_t st);
 int dpe_optim_trust_ratio(int kind, const void* desc, int ntensors, const int* first_chunk, int nchunks, const float* part_w,

@@ -7,6 +7,13 @@
 // (GPT-2 pads its vocab to a multiple of 64).  Per row: loss_i = lse - z_y.
 // dlogits (optional) = (softmax - onehot) * grad_scale, written in the
 // dtype requested (bf16 feeds the dgrad/wgrad GEMMs directly).
+//
+// REG (compile-time) adds label smoothing eps and the z-loss weight zl (kernel arguments):
+//   loss_i = (1 - eps)(lse - z_y) + eps (lse - mean_{j<V} z_j) + zl lse^2
+//   d/dz_j = p_j (1 + 2 zl lse) - (1 - eps)[j = y] - eps / V            (j < V; padding columns stay exact 0)
+// with one more per-thread accumulator, sum_{j<V}(z_j - m), in the pass that sums the exponentials: the
+// terms are bounded by the row's range and nothing cancels against V * m.  No further pass over the row.
+// The REG = false instantiations are the plain kernels, instruction for instruction.
 #include <algorithm>
 #include <type_traits>
 
@@ -22,11 +29,19 @@ DPE_DEVICE float ldv<float>(const float* p, int64_t i) { return p[i]; }
 template <>
 DPE_DEVICE float ldv<uint16_t>(const uint16_t* p, int64_t i) { return bf2f(p[i]); }
 
-template <typename TIn, typename TOut>
+// The REG arm's kernel arguments; empty for the plain kernels, whose argument block is then laid out as before.
+template <bool REG>
+struct CeReg {};
+template <>
+struct CeReg<true> {
+  float eps, zl;
+};
+
+template <typename TIn, typename TOut, bool REG>
 __global__ __launch_bounds__(1024) void ce_kernel(const TIn* __restrict__ logits, const int64_t* __restrict__ labels, int B,
                                                  int V, int64_t ld, float grad_scale, TOut* __restrict__ dlogits,
                                                  float* __restrict__ loss_rows, float* __restrict__ loss_sum,
-                                                 float* __restrict__ correct, int ignore_index) {
+                                                 float* __restrict__ correct, int ignore_index, CeReg<REG> ra) {
   __shared__ float sh[32];
   __shared__ int shi[32];
   const int row = blockIdx.x;
@@ -59,12 +74,19 @@ __global__ __launch_bounds__(1024) void ce_kernel(const TIn* __restrict__ logits
   }
   __syncthreads();
   // pass 2: sum exp
-  float s = 0.f;
-  for (int j = threadIdx.x; j < V; j += blockDim.x) s += __expf(ldv<TIn>(z, j) - m);
+  float s = 0.f, q = 0.f;  // q (REG): sum of z_j - m over the classes
+  for (int j = threadIdx.x; j < V; j += blockDim.x) {
+    const float t = ldv<TIn>(z, j) - m;
+    s += __expf(t);
+    if constexpr (REG) q += t;
+  }
   s = block_sum(s, sh);
+  if constexpr (REG) q = block_sum(q, sh);
   const float lse = m + __logf(s);
   const float zy = s_zy;  // published by the barriers inside block_sum
-  const float li = ignored ? 0.f : lse - zy;
+  float li = ignored ? 0.f : lse - zy;
+  if constexpr (REG)
+    li = ignored ? 0.f : (1.f - ra.eps) * (lse - zy) + ra.eps * (__logf(s) - q / (float)V) + ra.zl * lse * lse;
   if (threadIdx.x == 0) {
     if (loss_rows) loss_rows[row] = li;                 // summed in row order by ce_sum_kernel
     else if (loss_sum) atomicAdd(loss_sum, li);
@@ -72,10 +94,20 @@ __global__ __launch_bounds__(1024) void ce_kernel(const TIn* __restrict__ logits
   }
   if (dlogits) {
     TOut* d = dlogits + (int64_t)row * ld;
-    const float inv_s = 1.f / s;
+    float inv_s = 1.f / s;
+    [[maybe_unused]] float on = 1.f, off = 0.f;
+    if constexpr (REG) {
+      inv_s *= 1.f + 2.f * ra.zl * lse;
+      on = 1.f - ra.eps;
+      off = ra.eps / (float)V;
+    }
     for (int j = threadIdx.x; j < (int)ld; j += blockDim.x) {
       float g = 0.f;
-      if (j < V && !ignored) g = (__expf(ldv<TIn>(z, j) - m) * inv_s - (j == label ? 1.f : 0.f)) * grad_scale;
+      if constexpr (REG) {
+        if (j < V && !ignored) g = (__expf(ldv<TIn>(z, j) - m) * inv_s - off - (j == label ? on : 0.f)) * grad_scale;
+      } else {
+        if (j < V && !ignored) g = (__expf(ldv<TIn>(z, j) - m) * inv_s - (j == label ? 1.f : 0.f)) * grad_scale;
+      }
       if constexpr (sizeof(TOut) == 2) d[j] = f2bf(g);
       else d[j] = g;
     }
@@ -117,11 +149,25 @@ struct RowChunk<float> {
   }
 };
 
-template <typename TIn, typename TOut, int NT, int MAXC>
-__global__ __launch_bounds__(NT, NT >= 1024 ? 8 : 1) void ce_vec_kernel(const TIn* logits, const int64_t* __restrict__ labels, int V,
+// the REG arm's one extra reduction slot per wave (a function-local array: the plain instantiations have none)
+template <int NW>
+DPE_DEVICE float* ce_shq() {
+  __shared__ float q[NW];
+  return q;
+}
+
+// Waves per SIMD the 1024-thread REG kernels are bounded for.  The plain (1024, 8) kernel is held to 64 VGPRs
+// (8 waves: two blocks per CU) and spills a few; the REG arm's extra accumulator and constants would spill
+// more, so it is given the 128 VGPRs of one block per CU and keeps everything in registers.
+#ifndef DPE_CE_REG_WAVES
+#define DPE_CE_REG_WAVES 4
+#endif
+
+template <typename TIn, typename TOut, int NT, int MAXC, bool REG>
+__global__ __launch_bounds__(NT, NT >= 1024 ? (REG ? DPE_CE_REG_WAVES : 8) : 1) void ce_vec_kernel(const TIn* logits, const int64_t* __restrict__ labels, int V,
                                                     int64_t ld, float grad_scale, TOut* dlogits,
                                                     float* __restrict__ loss_rows, float* __restrict__ loss_sum,
-                                                    float* __restrict__ correct, int ignore_index) {
+                                                    float* __restrict__ correct, int ignore_index, CeReg<REG> ra) {
   constexpr int NW = NT / 64;
   constexpr float L2E = 1.4426950408889634f;
   __shared__ float shm[NW], shs[NW], shz[NW];
@@ -183,6 +229,7 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : 1) void ce_vec_kernel(const TI
   // exp(v - m) as one fma + the bare v_exp_f32 (arguments <= 0: results in (0, 1], denormals flush)
   const float mb = -m * L2E;
   float s = 0.f;
+  [[maybe_unused]] float q = 0.f;  // REG: sum of z_j - m over the classes (the padding is -inf here: skipped)
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     const int ch = tid + c * NT;
@@ -191,18 +238,38 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : 1) void ce_vec_kernel(const TI
       chunk(c, ch, f);
 #pragma unroll
       for (int e = 0; e < 8; ++e) s += __builtin_amdgcn_exp2f(fmaf(f[e], L2E, mb));
+      if constexpr (REG) {
+        if (ch * 8 + 8 <= V) {
+          q += ((f[0] - m) + (f[1] - m)) + ((f[2] - m) + (f[3] - m)) + (((f[4] - m) + (f[5] - m)) + ((f[6] - m) + (f[7] - m)));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (ch * 8 + e < V) q += f[e] - m;
+        }
+      }
     }
   }
   s = warp_sum(s);
   zy = warp_sum(zy);
   if (lane == 0) { shs[wid] = s; shz[wid] = zy; }
+  if constexpr (REG) {
+    q = warp_sum(q);
+    if (lane == 0) ce_shq<NW>()[wid] = q;
+  }
   __syncthreads();
   s = 0.f;
   zy = 0.f;
 #pragma unroll
   for (int w = 0; w < NW; ++w) { s += shs[w]; zy += shz[w]; }
   const float lse = m + __logf(s);
-  const float li = ignored ? 0.f : lse - zy;
+  float li = ignored ? 0.f : lse - zy;
+  if constexpr (REG) {
+    q = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) q += ce_shq<NW>()[w];
+    // lse - mean z = log(s) - q / V
+    li = ignored ? 0.f : (1.f - ra.eps) * (lse - zy) + ra.eps * (__logf(s) - q / (float)V) + ra.zl * lse * lse;
+  }
   if (tid == 0) {
     if (loss_rows) loss_rows[row] = li;                 // summed in row order by ce_sum_kernel
     else if (loss_sum) atomicAdd(loss_sum, li);
@@ -210,7 +277,14 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : 1) void ce_vec_kernel(const TI
   }
   if (dlogits) {
     TOut* d = dlogits + (int64_t)row * ld;
-    const float k = ignored ? 0.f : grad_scale / s;
+    float k = ignored ? 0.f : grad_scale / s;
+    float on = grad_scale;
+    [[maybe_unused]] float off = 0.f;
+    if constexpr (REG) {
+      k *= 1.f + 2.f * ra.zl * lse;
+      on = (1.f - ra.eps) * grad_scale;
+      off = ignored ? 0.f : ra.eps / (float)V * grad_scale;
+    }
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
       const int ch = tid + c * NT;
@@ -219,10 +293,20 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? 8 : 1) void ce_vec_kernel(const TI
         chunk(c, ch, f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) g[e] = __builtin_amdgcn_exp2f(fmaf(f[e], L2E, mb)) * k;
+        if constexpr (REG) {  // eps / V on the classes only: the padding keeps its exact 0
+          if (ch * 8 + 8 <= V) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g[e] -= off;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (ch * 8 + e < V) g[e] -= off;
+          }
+        }
         if (ch == lch && !ignored) {
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            if (e == (int)(label & 7)) g[e] -= grad_scale;
+            if (e == (int)(label & 7)) g[e] -= on;
         }
         if constexpr (sizeof(TOut) == 2) {
           *(u32x4*)(d + (int64_t)ch * 8) = pack8(g);
@@ -299,16 +383,16 @@ __global__ __launch_bounds__(256) void ce_grad_scale_kernel(const T* __restrict_
   }
 }
 
-template <typename TIn, typename TOut>
+template <bool REG, typename TIn, typename TOut>
 bool ce_vec_launch(const TIn* logits, const int64_t* labels, int B, int V, int64_t ld, float gs, TOut* d, float* lr,
-                   float* ls, float* cor, int ign, hipStream_t st) {
+                   float* ls, float* cor, int ign, CeReg<REG> ra, hipStream_t st) {
   if (ld % 8) return false;
   const int64_t nch = ld / 8;
 
 #define DPE_CE_VEC(NT, MC)                                                                                         \
   if (nch <= (int64_t)(NT) * (MC)) {                                                                               \
-    hipLaunchKernelGGL((ce_vec_kernel<TIn, TOut, NT, MC>), dim3(B), dim3(NT), 0, st, logits, labels, V, ld, gs, d, lr, \
-                       ls, cor, ign);                                                                              \
+    hipLaunchKernelGGL((ce_vec_kernel<TIn, TOut, NT, MC, REG>), dim3(B), dim3(NT), 0, st, logits, labels, V, ld, gs, d, \
+                       lr, ls, cor, ign, ra);                                                                 \
     return true;                                                                                                   \
   }
   DPE_CE_VEC(64, 1)
@@ -318,7 +402,11 @@ bool ce_vec_launch(const TIn* logits, const int64_t* labels, int B, int V, int64
   DPE_CE_VEC(1024, 1)
   DPE_CE_VEC(1024, 2)
   DPE_CE_VEC(1024, 4)
-  DPE_CE_VEC(1024, 8)
+  // an fp32 row of 8 chunks per thread is 64 VGPRs of logits alone: the REG arm leaves those rows (more than
+  // 32768 fp32 columns) to the three-pass kernel rather than spill
+  if constexpr (!(REG && sizeof(TIn) == 4)) {
+    DPE_CE_VEC(1024, 8)
+  }
 #undef DPE_CE_VEC
   return false;
 }
@@ -327,17 +415,47 @@ bool ce_vec_launch(const TIn* logits, const int64_t* labels, int B, int V, int64
 
 using namespace dpe;
 
+// one dtype pair: the row-in-registers kernel where the row fits it, else the three-pass one
+template <bool REG, typename TIn, typename TOut>
+static void ce_rows_typed(const TIn* logits, const int64_t* labels, int B, int V, int64_t ld, float grad_scale, TOut* dlogits,
+                          float* loss_rows, float* loss_sum, float* correct, int ignore_index, CeReg<REG> ra,
+                          hipStream_t st) {
+  if (ce_vec_launch<REG>(logits, labels, B, V, ld, grad_scale, dlogits, loss_rows, loss_sum, correct, ignore_index, ra, st))
+    return;
+  const int threads = V >= 4096 ? 1024 : 256;
+  hipLaunchKernelGGL((ce_kernel<TIn, TOut, REG>), dim3(B), dim3(threads), 0, st, logits, labels, B, V, ld, grad_scale, dlogits,
+                     loss_rows, loss_sum, correct, ignore_index, ra);
+}
+
+template <bool REG>
 static int dpe_cross_entropy_rows(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
                                   float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* loss_sum,
-                                  float* correct, int ignore_index, hipStream_t st);
+                                  float* correct, int ignore_index, CeReg<REG> ra, hipStream_t st) {
+  if (in_bf16) {
+    if (out_bf16)
+      ce_rows_typed<REG>((const uint16_t*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, st);
+    else
+      ce_rows_typed<REG>((const uint16_t*)logits, labels, B, V, ld, grad_scale, (float*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, st);
+  } else {
+    if (out_bf16)
+      ce_rows_typed<REG>((const float*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, st);
+    else
+      ce_rows_typed<REG>((const float*)logits, labels, B, V, ld, grad_scale, (float*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, st);
+  }
+  return 0;
+}
 
 // in_bf16 / out_bf16 select dtypes; dlogits may be null (eval)
 extern "C" int dpe_cross_entropy(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
                                  float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* loss_sum,
                                  float* correct, int ignore_index, hipStream_t st) {
   if (dlogits == logits && in_bf16 != out_bf16) return -2;  // in-place needs equal dtypes
-  const int rc = dpe_cross_entropy_rows(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16, loss_rows, loss_sum,
-                                        correct, ignore_index, st);
+  const int rc = dpe_cross_entropy_rows<false>(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16, loss_rows,
+                                               loss_sum, correct, ignore_index, CeReg<false>{}, st);
   if (rc == 0 && loss_rows && loss_sum)
     hipLaunchKernelGGL(ce_sum_kernel<false>, dim3(1), dim3(256), 0, st, loss_rows, B, loss_sum, (const int64_t*)nullptr, 0);
   return rc;
@@ -348,8 +466,21 @@ extern "C" int dpe_cross_entropy_mean(const void* logits, int in_bf16, const int
                                       float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* out4,
                                       int ignore_index, hipStream_t st) {
   if (dlogits == logits && in_bf16 != out_bf16) return -2;
-  const int rc = dpe_cross_entropy_rows(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16, loss_rows, out4,
-                                        out4 + 1, ignore_index, st);
+  const int rc = dpe_cross_entropy_rows<false>(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16, loss_rows, out4,
+                                               out4 + 1, ignore_index, CeReg<false>{}, st);
+  if (rc == 0) hipLaunchKernelGGL(ce_sum_kernel<true>, dim3(1), dim3(256), 0, st, loss_rows, B, out4, labels, ignore_index);
+  return rc;
+}
+
+// as dpe_cross_entropy_mean with label smoothing `eps` and z-loss weight `zl` (the REG kernels); the rows'
+// losses carry the regularisers, the reduction is the same kernel
+extern "C" int dpe_cross_entropy_mean_reg(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
+                                          float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* out4,
+                                          int ignore_index, float eps, float zl, hipStream_t st) {
+  if (dlogits == logits && in_bf16 != out_bf16) return -2;
+  if (!(eps >= 0.f && eps < 1.f && zl >= 0.f) || V <= 0) return -3;
+  const int rc = dpe_cross_entropy_rows<true>(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16, loss_rows, out4,
+                                              out4 + 1, ignore_index, CeReg<true>{eps, zl}, st);
   if (rc == 0) hipLaunchKernelGGL(ce_sum_kernel<true>, dim3(1), dim3(256), 0, st, loss_rows, B, out4, labels, ignore_index);
   return rc;
 }
@@ -363,36 +494,5 @@ extern "C" int dpe_ce_grad_scale(const void* d, void* o, int64_t n, int bf16, co
                        inv_n);
   else
     hipLaunchKernelGGL(ce_grad_scale_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)d, (float*)o, n, g, inv_n);
-  return 0;
-}
-
-static int dpe_cross_entropy_rows(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
-                                  float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* loss_sum,
-                                  float* correct, int ignore_index, hipStream_t st) {
-  if (in_bf16 ? (out_bf16 ? ce_vec_launch((const uint16_t*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits,
-                                           loss_rows, loss_sum, correct, ignore_index, st)
-                           : ce_vec_launch((const uint16_t*)logits, labels, B, V, ld, grad_scale, (float*)dlogits,
-                                           loss_rows, loss_sum, correct, ignore_index, st))
-              : (out_bf16 ? ce_vec_launch((const float*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits,
-                                          loss_rows, loss_sum, correct, ignore_index, st)
-                          : ce_vec_launch((const float*)logits, labels, B, V, ld, grad_scale, (float*)dlogits,
-                                          loss_rows, loss_sum, correct, ignore_index, st)))
-    return 0;
-  const int threads = V >= 4096 ? 1024 : 256;
-  if (in_bf16) {
-    if (out_bf16)
-      hipLaunchKernelGGL((ce_kernel<uint16_t, uint16_t>), dim3(B), dim3(threads), 0, st, (const uint16_t*)logits, labels, B, V,
-                         ld, grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct, ignore_index);
-    else
-      hipLaunchKernelGGL((ce_kernel<uint16_t, float>), dim3(B), dim3(threads), 0, st, (const uint16_t*)logits, labels, B, V, ld,
-                         grad_scale, (float*)dlogits, loss_rows, loss_sum, correct, ignore_index);
-  } else {
-    if (out_bf16)
-      hipLaunchKernelGGL((ce_kernel<float, uint16_t>), dim3(B), dim3(threads), 0, st, (const float*)logits, labels, B, V, ld,
-                         grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct, ignore_index);
-    else
-      hipLaunchKernelGGL((ce_kernel<float, float>), dim3(B), dim3(threads), 0, st, (const float*)logits, labels, B, V, ld,
-                         grad_scale, (float*)dlogits, loss_rows, loss_sum, correct, ignore_index);
-  }
   return 0;
 }

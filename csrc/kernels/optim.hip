@@ -276,6 +276,44 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------- learning-rate schedule
+// The lr of every group for this step, computed on the device from a device step counter and written into
+// the hp rows the update kernels read -- like the clip coefficient, so the host copies nothing per step and
+// a captured step replays with an advancing lr.  Schedule block `sched` (fp64):
+//   [0] s, the scheduled steps already taken   [1] kind (0 constant, 1 linear, 2 cosine, 3 poly)
+//   [2] W warm-up steps   [3] T total steps   [4] r = min_ratio   [5] power   [6 + g] base lr of group g
+//   f(s) = (s + 1) / W                                             s < W
+//        = 1 | 1 - (1 - r) t | r + (1 - r) (1 + cos(pi t)) / 2 | r + (1 - r) (1 - t)^power,
+//          t = min(1, (s - W) / max(1, T - W))                      otherwise
+// A thread per group evaluates f in fp64 and rounds base * f once; cur[g] keeps the lr the step uses.  The
+// counter then advances by this step's ok flag (final by now: the clip kernel runs first), so a step skipped
+// for a non-finite gradient norm consumes no schedule step.
+constexpr int SCHED_HDR = 6;
+
+__global__ __launch_bounds__(64) void lr_schedule_kernel(float* __restrict__ hp, int ngroups, double* __restrict__ sched,
+                                                         float* __restrict__ cur) {
+  const double s = sched[0], W = sched[2], T = sched[3], r = sched[4], pw = sched[5];
+  const int kind = (int)sched[1];
+  const float ok = hp[HP_OK];  // the same in every row
+  double f;
+  if (s < W) {
+    f = (s + 1.0) / W;
+  } else {
+    const double t = fmin(1.0, (s - W) / fmax(1.0, T - W));
+    if (kind == 1) f = 1.0 - (1.0 - r) * t;
+    else if (kind == 2) f = r + (1.0 - r) * (0.5 * (1.0 + cos(3.14159265358979323846 * t)));
+    else if (kind == 3) f = r + (1.0 - r) * pow(1.0 - t, pw);
+    else f = 1.0;
+  }
+  for (int g = threadIdx.x; g < ngroups; g += 64) {
+    const float lr = (float)(sched[SCHED_HDR + g] * f);
+    hp[g * HP] = lr;
+    cur[g] = lr;
+  }
+  __syncthreads();  // every thread has read s
+  if (threadIdx.x == 0) sched[0] = s + (double)ok;
+}
+
 // In-place g *= out[1] over the table (optim.clip_grad_norm_, for loops that keep torch's call).
 __global__ __launch_bounds__(256) void grad_scale_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
                                                          const float* __restrict__ out) {
@@ -592,6 +630,15 @@ extern "C" int dpe_optim_clip_coef(const float* partials, int nchunks, float* ou
                                    int ngroups, int skip, hipStream_t st) {
   hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, st, partials, nchunks > 0 ? nchunks : 0, out, max_norm, hp,
                      ngroups, skip);
+  return 0;
+}
+
+// This step's lr into hp[g * HP + 0] and cur[g], then the counter in sched[0] advances by hp[HP_OK].
+// sched holds SCHED_HDR + ngroups doubles (see lr_schedule_kernel).
+extern "C" int dpe_optim_sched_header() { return SCHED_HDR; }
+extern "C" int dpe_optim_lr_schedule(float* hp, int ngroups, double* sched, float* cur, hipStream_t st) {
+  if (ngroups <= 0) return 0;
+  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(64), 0, st, hp, ngroups, sched, cur);
   return 0;
 }
 

@@ -38,6 +38,8 @@ class GPT2Config:
     n_embd: int = 768
     dropout: float = 0.0
     bias: bool = True
+    label_smoothing: float = 0.0  # training-loss regularisers, inside the fused LM-head CE (Fx.lm_head_ce)
+    z_loss: float = 0.0
 
     @classmethod
     def tiny(cls, **kw):
@@ -134,7 +136,7 @@ class GPT2(nn.Module):
                 x = blk(x, doc)
         x = self.ln_f(x)
         if targets is not None:
-            return Fx.lm_head_ce(x, self.wte, targets)
+            return Fx.lm_head_ce(x, self.wte, targets, label_smoothing=self.cfg.label_smoothing, z_loss=self.cfg.z_loss)
         return Fx.lm_head(x, self.wte)
 
     def num_params(self) -> int:

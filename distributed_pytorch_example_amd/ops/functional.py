@@ -530,26 +530,48 @@ class _CEFn(Function):
     clamp / divide / cast kernels at the launch-bound forward -> backward seam."""
 
     @staticmethod
-    def forward(ctx, logits, labels, num_classes: int, ignore_index: int):
+    def forward(ctx, logits, labels, num_classes: int, ignore_index: int, label_smoothing: float = 0.0, z_loss: float = 0.0):
         out4, d = ext().cross_entropy_mean(logits.contiguous(), labels.contiguous(), num_classes,
-                                           logits.dtype == torch.bfloat16, ignore_index)
+                                           logits.dtype == torch.bfloat16, ignore_index,
+                                           label_smoothing=label_smoothing, z_loss=z_loss)
         ctx.save_for_backward(d, out4)
         return out4[2:3].reshape(())
 
     @staticmethod
     def backward(ctx, g):
         d, out4 = ctx.saved_tensors
-        return ext().ce_grad_scale(d, g.float().reshape(1), out4[3:4]), None, None, None
+        return ext().ce_grad_scale(d, g.float().reshape(1), out4[3:4]), None, None, None, None, None
 
 
-def cross_entropy(logits, labels, num_classes: Optional[int] = None, ignore_index: int = -100):
-    """Mean softmax cross-entropy over rows (torch.nn.CrossEntropyLoss semantics)."""
+def _check_ce_reg(label_smoothing: float, z_loss: float):
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+    if not z_loss >= 0.0:
+        raise ValueError(f"z_loss must be >= 0, got {z_loss}")
+
+
+def _ce_reference(logits, labels, ignore_index: int, label_smoothing: float, z_loss: float):
+    """The CPU branch: the regularised mean CE in plain torch ops (``logits``: [rows, classes])."""
+    loss = F.cross_entropy(logits, labels, ignore_index=ignore_index, label_smoothing=label_smoothing)
+    if z_loss != 0.0:
+        keep = labels != ignore_index
+        lse2 = torch.logsumexp(logits, dim=-1).square() * keep
+        loss = loss + z_loss * lse2.sum() / keep.sum().clamp(min=1)
+    return loss
+
+
+def cross_entropy(logits, labels, num_classes: Optional[int] = None, ignore_index: int = -100,
+                  label_smoothing: float = 0.0, z_loss: float = 0.0):
+    """Mean softmax cross-entropy over rows (torch.nn.CrossEntropyLoss semantics, ``label_smoothing`` included),
+    plus ``z_loss * mean(logsumexp^2)`` over the non-ignored rows."""
     if num_classes is None:
         num_classes = logits.shape[-1]
+    _check_ce_reg(label_smoothing, z_loss)
     if not logits.is_cuda:
-        return F.cross_entropy(logits.reshape(-1, logits.shape[-1])[:, :num_classes].float(), labels.reshape(-1),
-                               ignore_index=ignore_index)
-    return _CEFn.apply(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), num_classes, ignore_index)
+        return _ce_reference(logits.reshape(-1, logits.shape[-1])[:, :num_classes].float(), labels.reshape(-1),
+                             ignore_index, label_smoothing, z_loss)
+    return _CEFn.apply(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), num_classes, ignore_index,
+                       float(label_smoothing), float(z_loss))
 
 
 def cross_entropy_eval(logits, labels, num_classes: Optional[int] = None):
@@ -872,14 +894,15 @@ class _LMHeadCEFn(Function):
     """
 
     @staticmethod
-    def forward(ctx, x, wte, labels, pad_rows: int, ignore_index: int):
+    def forward(ctx, x, wte, labels, pad_rows: int, ignore_index: int, label_smoothing: float = 0.0, z_loss: float = 0.0):
         C = ext()
         w16 = shadow(wte, pad_rows)
         xb = x.contiguous() if x.dtype == torch.bfloat16 else x.to(torch.bfloat16).contiguous()
         xb = xb.reshape(-1, xb.shape[-1])
         logits = C.linear_fwd(xb, w16, None, 0, False, None, None)
         lab = labels.reshape(-1).contiguous()
-        out4, d = C.cross_entropy_mean(logits, lab, wte.shape[0], True, ignore_index, True)
+        out4, d = C.cross_entropy_mean(logits, lab, wte.shape[0], True, ignore_index, True,
+                                       label_smoothing=label_smoothing, z_loss=z_loss)
         ctx.save_for_backward(xb, d, out4)
         ctx.wte, ctx.pad, ctx.xshape = wte, pad_rows, x.shape
         note_use(wte)
@@ -894,17 +917,20 @@ class _LMHeadCEFn(Function):
         buf, direct = grad_sink(ctx.wte)
         C.linear_wgrad(d, xb, buf, 1.0, scale, None, 0, direct and grad_fresh(ctx.wte))
         grad_done(ctx.wte, direct)
-        return dx.reshape(ctx.xshape), (None if direct else buf), None, None, None
+        return dx.reshape(ctx.xshape), (None if direct else buf), None, None, None, None, None
 
 
-def lm_head_ce(x, wte, labels, vocab_pad_to: int = 64, ignore_index: int = -100):
-    """Mean CE of the tied LM head logits ``x @ wte^T`` against ``labels`` (fused)."""
+def lm_head_ce(x, wte, labels, vocab_pad_to: int = 64, ignore_index: int = -100, label_smoothing: float = 0.0,
+               z_loss: float = 0.0):
+    """Mean CE of the tied LM head logits ``x @ wte^T`` against ``labels`` (fused), optionally label-smoothed
+    and with ``z_loss * mean(logsumexp^2)``: both inside the CE kernel, the logits are not read again."""
+    _check_ce_reg(label_smoothing, z_loss)
     if not x.is_cuda:
         logits = F.linear(x.float(), wte)
-        return F.cross_entropy(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), ignore_index=ignore_index)
+        return _ce_reference(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), ignore_index, label_smoothing, z_loss)
     V = wte.shape[0]
     Vp = (V + vocab_pad_to - 1) // vocab_pad_to * vocab_pad_to
-    return _LMHeadCEFn.apply(x, wte, labels, Vp - V, ignore_index)
+    return _LMHeadCEFn.apply(x, wte, labels, Vp - V, ignore_index, float(label_smoothing), float(z_loss))
 
 
 def lm_head(x, wte, vocab_pad_to: int = 64):

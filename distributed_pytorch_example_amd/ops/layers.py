@@ -124,11 +124,15 @@ class LayerNorm(nn.Module):
 
 
 class CrossEntropyLoss(nn.Module):
-    """torch.nn.CrossEntropyLoss (mean) on the fused HIP kernel."""
+    """torch.nn.CrossEntropyLoss (mean, ``label_smoothing`` included) on the fused HIP kernel, plus an optional
+    ``z_loss * mean(logsumexp^2)``."""
 
-    def __init__(self, ignore_index: int = -100):
+    def __init__(self, ignore_index: int = -100, label_smoothing: float = 0.0, z_loss: float = 0.0):
         super().__init__()
+        Fx._check_ce_reg(label_smoothing, z_loss)
         self.ignore_index = ignore_index
+        self.label_smoothing = float(label_smoothing)
+        self.z_loss = float(z_loss)
 
     def forward(self, logits, target):
-        return Fx.cross_entropy(logits, target, None, self.ignore_index)
+        return Fx.cross_entropy(logits, target, None, self.ignore_index, self.label_smoothing, self.z_loss)

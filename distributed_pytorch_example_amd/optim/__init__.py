@@ -1,8 +1,8 @@
 import torch
 
-from .fused import LAMB, LARS, SGD, Adam, AdamW, _CLIP_BUF, _pack_desc
+from .fused import LAMB, LARS, SGD, Adam, AdamW, _CLIP_BUF, _pack_desc, lr_factor
 
-__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "build_optimizer", "clip_grad_norm_"]
+__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "build_optimizer", "clip_grad_norm_", "lr_factor"]
 
 
 def _trust_groups(params, weight_decay, off):
@@ -21,8 +21,16 @@ def _trust_groups(params, weight_decay, off):
 
 
 def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, momentum: float = 0.9, *,
-                    clip_grad_norm=None, skip_nonfinite: bool = False, trust_coefficient=None):
+                    clip_grad_norm=None, skip_nonfinite: bool = False, trust_coefficient=None, lr_schedule=None):
+    """``lr_schedule``: a dict of ``set_lr_schedule``'s arguments (``kind``, ``total_steps`` and optionally
+    ``warmup_steps``, ``min_ratio``, ``power``)."""
     name = name.lower()
+    if lr_schedule is not None:
+        lr_schedule = dict(lr_schedule)
+        unknown = set(lr_schedule) - {"kind", "warmup_steps", "total_steps", "min_ratio", "power"}
+        if unknown or "kind" not in lr_schedule:
+            raise ValueError(f"lr_schedule: a dict with 'kind', 'total_steps' and optionally 'warmup_steps', "
+                             f"'min_ratio', 'power'; got keys {sorted(lr_schedule)}")
     if trust_coefficient is not None and name not in ("lars", "lamb"):
         raise ValueError(f"trust_coefficient is for lars / lamb, not {name!r}")
     if name == "adam":
@@ -44,6 +52,8 @@ def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, mom
         raise ValueError(f"unknown optimizer {name!r}")
     if clip_grad_norm is not None or skip_nonfinite:
         opt.set_grad_clip(clip_grad_norm, skip_nonfinite=skip_nonfinite)
+    if lr_schedule is not None:
+        opt.set_lr_schedule(lr_schedule.pop("kind"), **lr_schedule)
     return opt
 
 

@@ -21,9 +21,14 @@ extra read of the gradients produces the norm on the device, a one-block
 kernel turns it into the clip coefficient inside the hyper-parameter block,
 and the update kernel multiplies every gradient by it.  The gradients are not
 written back, the host is not involved, and the step still replays in a graph.
+
+A learning-rate schedule (``set_lr_schedule``: warm-up, then constant / linear / cosine / polynomial decay)
+is evaluated on the device too: a one-block kernel turns a device step counter into this step's lr inside the
+hyper-parameter block, so no host copy happens per step and a captured step replays with an advancing lr.
 """
 from __future__ import annotations
 
+import math
 import struct
 
 import torch
@@ -33,6 +38,27 @@ from ..ops import _state
 
 _HP = 12
 _CLIP_BUF = 5  # device clip block: total_norm, coef, ok, skipped steps | max_norm
+_SCHED_KINDS = {"constant": 0, "linear": 1, "cosine": 2, "poly": 3}  # lr_schedule_kernel's kind
+
+
+def _sched_header() -> int:
+    return int(ext().optim_sched_header())
+
+
+def lr_factor(s: int, kind: str, warmup_steps: int, total_steps: int, min_ratio: float = 0.0, power: float = 1.0) -> float:
+    """The schedule's factor for the step taken after ``s`` scheduled steps (``set_lr_schedule``), in Python
+    floats: what csrc/kernels/optim.hip's lr_schedule_kernel evaluates on the device."""
+    W, T, r = warmup_steps, total_steps, min_ratio
+    if s < W:
+        return (s + 1.0) / W
+    t = min(1.0, (s - W) / max(1.0, float(T - W)))
+    if kind == "linear":
+        return 1.0 - (1.0 - r) * t
+    if kind == "cosine":
+        return r + (1.0 - r) * (0.5 * (1.0 + math.cos(math.pi * t)))
+    if kind == "poly":
+        return r + (1.0 - r) * (1.0 - t) ** power
+    return 1.0
 
 
 def _pack_desc(p, g, s1, s2, sh, n, group, ti):
@@ -64,6 +90,121 @@ class _FusedMixin:
         self._trust_tab = None  # (first_chunk, part_w, part_x), allocated with the table
         self._trust_stats = None
         self._trust_ran = False
+        self._sched_cfg = None  # set_lr_schedule(): (kind, warmup_steps, total_steps, min_ratio, power)
+        self._sched = None  # device schedule block (fp64): counter, the arguments, one base lr per group
+        self._sched_key = None
+        self._sched_cur = None  # fp32 [n_groups]: the lr of the last scheduled step
+        self._sched_ran = False
+        self._sched_last = 0  # the counter while there is no device block (CPU path, a freshly loaded state)
+
+    # ------------------------------------------------------ learning-rate schedule
+    def set_lr_schedule(self, kind, *, warmup_steps: int = 0, total_steps=None, min_ratio: float = 0.0,
+                        power: float = 1.0) -> None:
+        """Scale every group's lr by ``f(s)`` in every following ``step()``; ``s`` counts the steps taken under
+        the schedule (0 for the first).  ``kind`` is "constant", "linear", "cosine" or "poly"; ``None`` turns the
+        schedule off and the base lr is used again.  With ``W = warmup_steps``, ``T = total_steps``,
+        ``r = min_ratio``: ``f = (s + 1) / W`` while ``s < W``; afterwards, with
+        ``t = min(1, (s - W) / max(1, T - W))``, constant ``1``, linear ``1 - (1 - r) t``, cosine
+        ``r + (1 - r) (1 + cos(pi t)) / 2``, poly ``r + (1 - r) (1 - t)^power`` (past ``T`` it holds at ``r``).
+        ``group["lr"]`` stays the base lr.  On GPU the factor is evaluated on the device from a device counter
+        (no host copy per step; a captured step replays with an advancing lr); a step skipped by
+        ``skip_nonfinite`` consumes no schedule step.  Setting a schedule again keeps the counter."""
+        if kind is None:
+            self._sched_cfg = None
+            self._sched_ran = False
+            self._hp_key = None  # the next step writes the base lr back into the hp rows
+            return
+        if kind not in _SCHED_KINDS:
+            raise ValueError(f"set_lr_schedule: kind must be one of {sorted(_SCHED_KINDS)} or None, got {kind!r}")
+        if total_steps is None:
+            raise ValueError("set_lr_schedule: total_steps is required")
+        W, T, r, pw = int(warmup_steps), int(total_steps), float(min_ratio), float(power)
+        if W < 0:
+            raise ValueError(f"set_lr_schedule: warmup_steps must be >= 0, got {warmup_steps}")
+        if not T > W:
+            raise ValueError(f"set_lr_schedule: total_steps ({total_steps}) must exceed warmup_steps ({warmup_steps})")
+        if not 0.0 <= r <= 1.0:
+            raise ValueError(f"set_lr_schedule: min_ratio must be in [0, 1], got {min_ratio}")
+        if not pw > 0.0:
+            raise ValueError(f"set_lr_schedule: power must be > 0, got {power}")
+        self._sched_cfg = (kind, W, T, r, pw)
+        if self._sched is not None:
+            self._write_sched()  # device values, like max_norm: a captured step picks them up on replay
+
+    def _sched_block(self):
+        """The device schedule block, made on first use with the counter a loaded state left."""
+        n = _sched_header() + len(self.param_groups)
+        if self._sched is None or self._sched.numel() != n:
+            dev = self._all_params()[0].device
+            if self._sched is not None:
+                self._sched_last = int(self._sched[0].item())
+            self._sched = torch.zeros(n, dtype=torch.float64, device=dev)
+            self._sched[0].fill_(float(self._sched_last))
+            self._sched_cur = torch.zeros(len(self.param_groups), dtype=torch.float32, device=dev)
+            self._sched_key = None
+        return self._sched
+
+    def _write_sched(self):
+        """The schedule's arguments and the groups' base lrs into the device block, when they changed."""
+        kind, W, T, r, pw = self._sched_cfg
+        vals = [float(_SCHED_KINDS[kind]), float(W), float(T), r, pw] + [_lr(g) for g in self.param_groups]
+        key = tuple(vals)
+        sched = self._sched_block()
+        if key != self._sched_key:
+            sched[1:].copy_(torch.tensor(vals, dtype=torch.float64))
+            self._sched_key = key
+
+    def _sched_launch(self):
+        """This step's lr into the hp rows (after the step's ok flag is final, before the first kernel that
+        reads lr); the device counter advances by the ok flag."""
+        if self._sched_cfg is not None:
+            if self._sched_key is None:  # a schedule first set on a graph_safe optimizer: no block yet
+                self._write_sched()
+            ext().optim_lr_schedule(self._hp, self._sched, self._sched_cur)
+            self._sched_ran = True
+
+    @property
+    def current_lr(self):
+        """fp32 ``[n_groups]`` on the parameters' device: the lr the last scheduled step used.  ``None`` before
+        the first scheduled step.  Reading it does not synchronise."""
+        return self._sched_cur if self._sched_ran else None
+
+    @property
+    def schedule_step(self):
+        """0-d fp64 counter on the parameters' device: the steps taken under the schedule."""
+        if self._sched is not None:
+            return self._sched[0]
+        ps = self._all_params()
+        if ps and ps[0].is_cuda:
+            return self._sched_block()[0]
+        return torch.tensor(float(self._sched_last), dtype=torch.float64)
+
+    def _cpu_sched_begin(self):
+        """CPU path: put ``base * f(s)`` into ``group["lr"]`` for the duration of the step."""
+        if self._sched_cfg is None:
+            return None
+        f = lr_factor(self._sched_last, *self._sched_cfg)
+        base = [g["lr"] for g in self.param_groups]
+        for g in self.param_groups:
+            g["lr"] = _lr(g) * f
+        self._sched_cur = torch.tensor([g["lr"] for g in self.param_groups], dtype=torch.float32)
+        return base
+
+    def _cpu_sched_end(self, base):
+        if base is not None:
+            for g, b in zip(self.param_groups, base):
+                g["lr"] = b
+            self._sched_last += 1
+            self._sched_ran = True
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self._sched_cfg is not None:
+            kind, W, T, r, pw = self._sched_cfg
+            last = int(self._sched[0].item()) if self._sched is not None else int(self._sched_last)
+            sd["lr_schedule"] = {"kind": kind, "warmup_steps": W, "total_steps": T, "min_ratio": r, "power": pw,
+                                 "last_step": last}
+        return sd
 
     # ------------------------------------------------------ gradient clipping
     def set_grad_clip(self, max_norm, *, skip_nonfinite: bool = False) -> None:
@@ -243,6 +384,14 @@ class _FusedMixin:
         self._tab = None
         self._tab_key = None
         self._hp_key = None
+        ls = state_dict.get("lr_schedule")
+        if ls is not None:  # the checkpoint's schedule and counter; a state dict without one changes neither
+            self.set_lr_schedule(ls["kind"], warmup_steps=ls["warmup_steps"], total_steps=ls["total_steps"],
+                                 min_ratio=ls["min_ratio"], power=ls["power"])
+            self._sched_last = int(ls["last_step"])
+            if self._sched is not None:
+                self._sched[0].fill_(float(self._sched_last))
+            self._sched_ran = False
 
     def _hp_row(self, g):
         raise NotImplementedError
@@ -299,6 +448,9 @@ class _FusedMixin:
                     self._build_table()
                     self._tab_key = key
                 self._write_hp()
+                if self._sched_cfg is not None:
+                    self._write_sched()
+                    self._sched_launch()  # nothing grid-wide precedes the update here: ok is the host's 1.0
                 self._steps.add_(1.0)
             self._ov_open, self._ov_done = True, set()
         tis = sorted({self._ti[id(p)] for p in params if id(p) in self._ti} - self._ov_done)
@@ -323,6 +475,8 @@ class _FusedMixin:
                 self._build_table()
                 self._tab_key = key
             self._write_hp()
+            if self._sched_cfg is not None:
+                self._write_sched()
         d, ck = self._tab
         if self._trust is not None:
             self._trust_step(d, ck)
@@ -336,6 +490,7 @@ class _FusedMixin:
             self._steps.add_(buf[2] if self._clip_skip else 1.0)
         else:
             self._steps.add_(1.0)
+        self._sched_launch()
         ext().optim_step(self._kind, d, ck, self._hp, self._steps)
         _state.after_optimizer_step()
 
@@ -357,6 +512,7 @@ class _FusedMixin:
         if clip:
             self._clip_ran = True
         self._steps.add_(buf[2] if clip and self._clip_skip else 1.0)  # a skipped step advances no counter
+        self._sched_launch()  # ok is final; LARS's update and LAMB's phase 2 (the readers of lr) come after
         if self._trust == 1:
             C.optim_trust_partials(1, d, ck, self._hp, self._steps, pw, px)
         C.optim_trust_ratio(self._trust, d, first, nck, pw, px, self._hp, self._trust_stats)
@@ -425,7 +581,11 @@ class Adam(_FusedMixin, torch.optim.Adam):
             return loss
         if not self._cpu_clip():
             return None
-        return super().step()
+        base = self._cpu_sched_begin()
+        try:
+            return super().step()
+        finally:
+            self._cpu_sched_end(base)
 
 
 class AdamW(Adam):
@@ -463,7 +623,11 @@ class SGD(_FusedMixin, torch.optim.SGD):
             return loss
         if not self._cpu_clip():
             return None
-        return super().step()
+        base = self._cpu_sched_begin()
+        try:
+            return super().step()
+        finally:
+            self._cpu_sched_end(base)
 
 
 class LARS(SGD):
@@ -512,6 +676,14 @@ class LARS(SGD):
             return loss
         if not self._cpu_clip():
             return None
+        base = self._cpu_sched_begin()
+        try:
+            self._cpu_update()
+        finally:
+            self._cpu_sched_end(base)
+        return loss
+
+    def _cpu_update(self):
         rows = []
         for group in self.param_groups:
             lr, mom, damp, wd = _lr(group), group["momentum"], group["dampening"], group["weight_decay"]
@@ -536,7 +708,6 @@ class LARS(SGD):
                     d = d.add(buf, alpha=mom) if group["nesterov"] else buf
                 p.add_(d, alpha=-lr)
         self._cpu_stats(rows)
-        return loss
 
 
 class LAMB(Adam):
@@ -577,6 +748,14 @@ class LAMB(Adam):
             return loss
         if not self._cpu_clip():
             return None
+        base = self._cpu_sched_begin()
+        try:
+            self._cpu_update()
+        finally:
+            self._cpu_sched_end(base)
+        return loss
+
+    def _cpu_update(self):
         rows = []
         for group in self.param_groups:
             lr, (b1, b2), eps, wd = _lr(group), group["betas"], group["eps"], group["weight_decay"]
@@ -601,4 +780,3 @@ class LAMB(Adam):
                 rows.append([float(wn), float(un), float(ratio)])
                 p.add_(u * ratio, alpha=-lr)
         self._cpu_stats(rows)
-        return loss

@@ -58,6 +58,18 @@ def build_parser() -> argparse.ArgumentParser:
                    help="clip gradients to this global 2-norm inside the optimizer step (default: off)")
     p.add_argument("--skip-nonfinite-steps", action="store_true",
                    help="with --clip-grad-norm: a step whose gradient norm is inf/NaN changes nothing")
+    p.add_argument("--lr-schedule", default=None, choices=["constant", "linear", "cosine", "poly"],
+                   help="scale --lr per optimizer step, on the device: linear warm-up over --warmup-steps, then this decay "
+                        "down to --lr-min-ratio at the run's last step (epochs x optimizer steps per epoch); default: off")
+    p.add_argument("--warmup-steps", type=int, default=None, help="with --lr-schedule: warm-up steps (default 0)")
+    p.add_argument("--lr-min-ratio", type=float, default=None,
+                   help="with --lr-schedule: the factor the decay ends at, in [0, 1] (default 0)")
+    p.add_argument("--lr-power", type=float, default=None, help="with --lr-schedule poly: the exponent (default 1)")
+    p.add_argument("--label-smoothing", type=float, default=0.0,
+                   help="label smoothing of the training loss, in [0, 1), inside the fused cross-entropy kernel; the "
+                        "validation loss stays the plain cross-entropy, the logged train loss includes the regularisers")
+    p.add_argument("--z-loss", type=float, default=0.0,
+                   help="weight of the z-loss (mean logsumexp^2) added to the training loss; validation stays plain")
     p.add_argument("--bucket-mb", type=float, default=None,
                    help="gradient bucket cap (default: the 7-link xGMI policy, parallel/buckets.py)")
     p.add_argument("--last-bucket-mb", type=float, default=None,
@@ -173,6 +185,26 @@ def validate(model, loader, criterion, device, num_classes, max_steps=None, watc
     return (total_loss / max(1, nbatches)).item(), (100.0 * correct / max(1, total)).item()
 
 
+def schedule_total_steps(epochs: int, batches_per_epoch: int, max_steps=None, grad_accum: int = 1) -> int:
+    """Optimizer steps of the whole run: per epoch ``ceil(min(batches, max_steps) / grad_accum)`` -- the epoch's
+    last micro-batch always steps (``train_epoch``'s ``sync``)."""
+    n_eff = min(batches_per_epoch, max_steps) if max_steps is not None else batches_per_epoch
+    return epochs * -(-n_eff // max(1, grad_accum))
+
+
+def _lr_schedule_kw(parser, args, batches_per_epoch: int):
+    """--lr-schedule and friends -> ``build_optimizer``'s ``lr_schedule`` dict (None: no schedule)."""
+    if args.lr_schedule is None:
+        return None
+    total = schedule_total_steps(args.epochs, batches_per_epoch, args.max_steps, args.grad_accum)
+    warmup = args.warmup_steps or 0
+    if warmup >= total:
+        parser.error(f"--warmup-steps {warmup} is not shorter than the run's {total} optimizer steps")
+    return {"kind": args.lr_schedule, "warmup_steps": warmup, "total_steps": total,
+            "min_ratio": 0.0 if args.lr_min_ratio is None else args.lr_min_ratio,
+            "power": 1.0 if args.lr_power is None else args.lr_power}
+
+
 def _dtype_kw(args) -> dict:
     """--dtype -> model kwargs: SimpleNet runs fp32 (reference) or bf16; the BASELINE-scope models are bf16."""
     if args.model == "simplenet":
@@ -196,6 +228,20 @@ def main(argv=None):
         parser.error("--doc-len-mean must be >= 1")
     if args.trust_coefficient is not None and args.optimizer not in ("lars", "lamb"):
         parser.error("--trust-coefficient needs --optimizer lars or lamb")
+    if args.lr_schedule is None:
+        for flag, v in (("--warmup-steps", args.warmup_steps), ("--lr-min-ratio", args.lr_min_ratio), ("--lr-power", args.lr_power)):
+            if v is not None:
+                parser.error(f"{flag} needs --lr-schedule")
+    if args.warmup_steps is not None and args.warmup_steps < 0:
+        parser.error("--warmup-steps must be >= 0")
+    if args.lr_min_ratio is not None and not 0.0 <= args.lr_min_ratio <= 1.0:
+        parser.error("--lr-min-ratio must be in [0, 1]")
+    if args.lr_power is not None and not args.lr_power > 0:
+        parser.error("--lr-power must be > 0")
+    if not 0.0 <= args.label_smoothing < 1.0:
+        parser.error("--label-smoothing must be in [0, 1)")
+    if not args.z_loss >= 0.0:
+        parser.error("--z-loss must be >= 0")
     ensure_single_process_env()
     rank, world_size, local_rank = pdist.init_process_group(args.backend, comm_max_channels=args.comm_max_channels)
     logger.info(f"Initialized process group: rank={rank}, world_size={world_size}, local_rank={local_rank}")
@@ -204,7 +250,8 @@ def main(argv=None):
     logger.info(f"Starting distributed training with {world_size} processes")
     logger.info(f"Configuration: epochs={args.epochs}, batch_size={args.batch_size}, lr={args.lr}")
 
-    model = get_model(args.model, **_dtype_kw(args)).to(device)
+    reg_kw = {"label_smoothing": args.label_smoothing, "z_loss": args.z_loss}
+    model = get_model(args.model, **_dtype_kw(args), **(reg_kw if args.model.startswith("gpt2") else {})).to(device)
     model = DDP(model, bucket_cap_mb=args.bucket_mb,
                 last_bucket_mb="auto" if args.last_bucket_mb is None else (args.last_bucket_mb or None),
                 gradient_compression=None if args.gradient_compression == "none" else args.gradient_compression,
@@ -225,10 +272,11 @@ def main(argv=None):
     opt_name = args.optimizer or ("adam" if args.model == "simplenet" else ("sgd" if args.model.startswith("resnet") else "adamw"))
     optimizer = build_optimizer(opt_name, model.parameters(), lr=args.lr, weight_decay=args.weight_decay,
                                 clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps,
+                                lr_schedule=_lr_schedule_kw(parser, args, len(train_loader)),
                                 **({"trust_coefficient": args.trust_coefficient} if opt_name in ("lars", "lamb") else {}))
 
-    def criterion(out, tgt):
-        return Fx.cross_entropy(out, tgt, num_classes)
+    def criterion(out, tgt):  # training only: validate() takes Fx.cross_entropy_eval, the plain cross-entropy
+        return Fx.cross_entropy(out, tgt, num_classes, label_smoothing=args.label_smoothing, z_loss=args.z_loss)
 
     start_epoch = 0
     if rank == 0:
@@ -273,6 +321,9 @@ def main(argv=None):
                     r = optimizer.trust_stats[:, 2].cpu()[on]
                     logger.info(f"  Trust ratio (last step): min {r.min().item():.4g}, median {r.median().item():.4g}, "
                                 f"max {r.max().item():.4g}")
+            if getattr(optimizer, "current_lr", None) is not None:
+                logger.info("  LR (last step): " + ", ".join(f"{v:.6g}" for v in optimizer.current_lr.tolist())
+                            + f", schedule step: {int(optimizer.schedule_step.item())}")
             # no step heartbeat while rank 0 writes (RCCL async errors are still polled)
             with (watchdog.suspended() if watchdog is not None else _null()):
                 if avg_val_accuracy > best_accuracy:
