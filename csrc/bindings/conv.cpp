@@ -690,6 +690,29 @@ std::vector<Tensor> conv_fwd(const Tensor& x, const Tensor& w, std::vector<int64
 // DPE_DGRAD_FWD=0: stride-1 data grads on the transposed-filter loaders (A/B reference)
 bool dgrad_as_fwd() { static const bool on = env_on("DPE_DGRAD_FWD", true); return on; }
 
+// dy of a data / weight grad must be the forward conv's output for this input size: OH, OW from H, W, stride, pad
+// and dilation as conv_fwd computes them.  pad [top, left, bottom, right]: exactly that size.  pad [ph, pw] names
+// the top / left pad only (the bottom / right one is whatever produced dy: the s2d stem passes [2, 2] for its
+// [2, 2, 1, 1]), so the size with a bottom / right pad of ph / pw or of one less is accepted.  A dy of any other
+// size would be walked with a pixel grid that is not the conv's (wrong gradients, nothing to catch them downstream).
+void check_dy_shape(const char* op, const Tensor& dy, const dpe::ConvGeom& g, const std::vector<int64_t>& pad) {
+  TORCH_CHECK(pad.size() == 2 || pad.size() == 4, op, ": pad is [ph, pw] or [top, left, bottom, right]");
+  TORCH_CHECK(g.sh >= 1 && g.sw >= 1 && g.dh >= 1 && g.dw >= 1 && g.ph >= 0 && g.pw >= 0, op, ": bad stride / pad / dilation");
+  auto out = [](int64_t in, int64_t p0, int64_t p1, int64_t d, int64_t k, int64_t s) -> int64_t {
+    const int64_t span = in + p0 + p1 - d * (k - 1) - 1;
+    return span < 0 ? 0 : span / s + 1;
+  };
+  const bool four = pad.size() == 4;
+  const int64_t oh_hi = out(g.H, g.ph, four ? pad[2] : g.ph, g.dh, g.R, g.sh), oh_lo = four ? oh_hi : out(g.H, g.ph, std::max(g.ph - 1, 0), g.dh, g.R, g.sh);
+  const int64_t ow_hi = out(g.W, g.pw, four ? pad[3] : g.pw, g.dw, g.S, g.sw), ow_lo = four ? ow_hi : out(g.W, g.pw, std::max(g.pw - 1, 0), g.dw, g.S, g.sw);
+  TORCH_CHECK(dy.dim() == 4 && dy.size(1) >= std::max<int64_t>(1, oh_lo) && dy.size(1) <= oh_hi &&
+                  dy.size(2) >= std::max<int64_t>(1, ow_lo) && dy.size(2) <= ow_hi,
+              op, ": dy is [", dy.size(0), ", ", dy.size(1), ", ", dy.size(2), ", ", dy.size(3), "] but an input of ", g.H, " x ",
+              g.W, " with a ", g.R, " x ", g.S, " filter, stride (", g.sh, ", ", g.sw, "), pad (", g.ph, ", ", g.pw,
+              four ? ", ...)" : ")", ", dilation (", g.dh, ", ", g.dw, ") gives OH in [", oh_lo, ", ", oh_hi, "], OW in [", ow_lo,
+              ", ", ow_hi, "]");
+}
+
 void conv_wgrad(const Tensor& dy, const Tensor& x, Tensor& dw, std::vector<int64_t> stride, std::vector<int64_t> pad,
                 std::vector<int64_t> dil, double alpha, const c10::optional<Tensor>& in_coef, int64_t fin_stream,
                 bool deterministic, bool overwrite);
@@ -711,6 +734,7 @@ std::vector<Tensor> conv_dgrad_impl(const Tensor& dy, const Tensor& w, std::vect
   Tensor dx = acc_into ? *acc_into : at::empty(xshape, dy.options());
   auto g = geom(dx, w, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], dy.size(1), dy.size(2));
   TORCH_CHECK(dy.size(3) == g.K && dy.size(0) == g.N, "conv_dgrad: dy shape mismatch");
+  check_dy_shape("conv_dgrad", dy, g, pad);
   auto a = base_args();
   a.g = g;
   a.A = bp(dy); a.B = bp(w); a.C = dx.data_ptr();
@@ -987,6 +1011,7 @@ void conv_wgrad(const Tensor& dy, const Tensor& x, Tensor& dw, std::vector<int64
   CHECK_GPU(dy); CHECK_BF16(dy); CHECK_BF16(x); CHECK_CONTIG(dy); CHECK_CONTIG(x); CHECK_F32(dw); CHECK_CONTIG(dw);
   auto g = geom(x, dw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], dy.size(1), dy.size(2));
   TORCH_CHECK(dy.size(3) == g.K && dy.size(0) == g.N, "conv_wgrad: dy shape mismatch");
+  check_dy_shape("conv_wgrad", dy, g, pad);
   auto a = base_args();
   a.g = g;
   a.A = bp(dy); a.B = bp(x); a.C = dw.data_ptr();
