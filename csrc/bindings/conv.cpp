@@ -484,7 +484,9 @@ void linear_wgrad(const Tensor& dy, const Tensor& x, Tensor& dw, double alpha, c
   TORCH_CHECK(ldy % 8 == 0 && K % 8 == 0, "linear_wgrad: dy row stride and in_features must be multiples of 8");
   const int64_t M = dy.numel() / ldy;
   if (M % 64 == 0) {
-    // TN: A = dy^T (M-contiguous, loads may read dy's zero pad columns up to ldy), B = x (N-contiguous)
+    // TN: A = dy^T (M-contiguous), B = x (N-contiguous).  The loads of A stop at a_dim = round8(N) (hgemm.hip
+    // stage_setup clamps every 16-B chunk to it): the pad columns [N, a_dim) are read (zero by the contract above), the
+    // columns [a_dim, ldy) are never read and need no fill
     auto a = hargs();
     a.A = bp(dy); a.B = bp(x); a.C = dw.data_ptr();
     a.M = (int)N; a.N = (int)K; a.K = (int)M;

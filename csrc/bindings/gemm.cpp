@@ -153,6 +153,7 @@ Plan plan(int64_t M, int64_t N, int64_t K, int ak, int bk, bool allow_split, int
   const int reserve = dpe_cu_reserve();
   const int64_t ktiles = K / 64;
   Plan best{-1, 1, (int)K, 0, 1e30};
+  if (ktiles < 1) return best;  // K < 64, no K-tile: kt below would be 0 and the split arithmetic divide by it
   if (force_cfg < 0) force_cfg = g_force_cfg;
   if (force_splits < 0) force_splits = g_force_splits;
   for (const TileCfg& c : kTiles) {
