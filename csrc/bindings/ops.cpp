@@ -126,6 +126,42 @@ Tensor dropout(const Tensor& x, double p, int64_t seed, int64_t offset) {
   return y;
 }
 
+// rng: the device dropout state, int64[2] (seed, offset), read by the kernels
+const int64_t* rng_ptr(const Tensor& rng, const Tensor& like, const char* what) {
+  TORCH_CHECK(rng.is_cuda() && rng.device() == like.device() && rng.scalar_type() == at::kLong && rng.dim() == 1 &&
+                  rng.numel() == 2 && rng.is_contiguous(),
+              what, ": rng must be a contiguous int64[2] tensor on the input's device");
+  return (const int64_t*)rng.data_ptr();
+}
+
+Tensor dropout_add(const Tensor& res, const Tensor& y, double p, const Tensor& rng, int64_t stream,
+                   const c10::optional<Tensor>& out_) {
+  CHECK_GPU(res); CHECK_F32(res); CHECK_CONTIG(res); CHECK_GPU(y); CHECK_CONTIG(y);
+  const bool bf = y.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || y.scalar_type() == at::kFloat, "dropout_add: y is f32 or bf16");
+  TORCH_CHECK(y.numel() == res.numel() && y.device() == res.device(), "dropout_add: res and y differ in size or device");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_add: p must be in [0, 1), got ", p);
+  TORCH_CHECK(stream >= 0 && stream <= 0xffffffffLL, "dropout_add: stream must fit 32 bits");
+  Tensor out = has(out_) ? *out_ : at::empty_like(res);
+  CHECK_GPU(out); CHECK_F32(out); CHECK_CONTIG(out);
+  TORCH_CHECK(out.numel() == res.numel() && out.device() == res.device(), "dropout_add: out must have res's size and device");
+  CHECK_RC(dpe_dropout_add(fp(res), y.data_ptr(), bf ? 1 : 0, fp(out), res.numel(), (float)p,
+                           rng_ptr(rng, res, "dropout_add"), (uint32_t)stream, cur_stream()), "dropout_add");
+  return out;
+}
+
+Tensor dropout_cast(const Tensor& g, double p, const Tensor& rng, int64_t stream, const c10::optional<Tensor>& out_) {
+  CHECK_GPU(g); CHECK_F32(g); CHECK_CONTIG(g);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_cast: p must be in [0, 1), got ", p);
+  TORCH_CHECK(stream >= 0 && stream <= 0xffffffffLL, "dropout_cast: stream must fit 32 bits");
+  Tensor out = has(out_) ? *out_ : at::empty_like(g, g.options().dtype(at::kBFloat16));
+  CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out);
+  TORCH_CHECK(out.numel() == g.numel() && out.device() == g.device(), "dropout_cast: out must have g's size and device");
+  CHECK_RC(dpe_dropout_cast(fp(g), bpm(out), g.numel(), (float)p, rng_ptr(rng, g, "dropout_cast"),
+                            (uint32_t)stream, cur_stream()), "dropout_cast");
+  return out;
+}
+
 Tensor add(const Tensor& a, const Tensor& b, double alpha) {
   CHECK_GPU(a); CHECK_CONTIG(a); CHECK_CONTIG(b);
   TORCH_CHECK(a.scalar_type() == b.scalar_type() && a.numel() == b.numel(), "add: mismatch");
@@ -408,9 +444,25 @@ void layernorm_bwd_finalize_group(const std::vector<Tensor>& parts, const std::v
 // ---------------------------------------------------------------- attention
 // qkv: [B, T, 3, H, D] bf16 -> out [B, T, H, D] bf16, lse [B, H, T] f32 (both optionally caller-allocated).
 // doc_start / doc_end (int32 [B, T], together): the packed-document mask doc_start[b, i] <= j <= i.
+// dropout_p > 0: dropout on P inside the kernels at the 8-bit rate thr / 256, thr = clamp(round(256 p), 1, 255); rng is
+// the device int64[2] (seed, offset) the kernels read, stream the call site (Philox counter_lo).  0 = today's kernels.
+const int64_t* drop_rng(double p, const c10::optional<Tensor>& rng, int64_t stream, const Tensor& like, uint32_t* thr) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout_p must be in [0, 1), got ", p);
+  TORCH_CHECK(stream >= 0 && stream <= 0xffffffffLL, "attn: stream must fit 32 bits");
+  *thr = 0;
+  if (p == 0.0) return nullptr;
+  TORCH_CHECK(has(rng), "attn: dropout_p > 0 needs rng (device int64[2]: seed, offset)");
+  TORCH_CHECK(rng->is_cuda() && rng->device() == like.device(), "attn: rng must be on qkv's device");
+  TORCH_CHECK(rng->scalar_type() == at::kLong && rng->dim() == 1 && rng->numel() == 2 && rng->is_contiguous(),
+              "attn: rng must be a contiguous int64[2] tensor");
+  *thr = (uint32_t)std::min(255.0, std::max(1.0, std::floor(256.0 * p + 0.5)));
+  return (const int64_t*)rng->data_ptr();
+}
+
 std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal, const c10::optional<Tensor>& out_,
                              const c10::optional<Tensor>& lse_, const c10::optional<Tensor>& doc_start,
-                             const c10::optional<Tensor>& doc_end) {
+                             const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng,
+                             int64_t stream) {
   CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_CONTIG(qkv);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   TORCH_CHECK(qkv.numel() == B * T * 3 * H * D, "attn: qkv must be [B,T,3,H,D]");
@@ -420,6 +472,14 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool ca
   CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out); CHECK_GPU(lse); CHECK_F32(lse); CHECK_CONTIG(lse);
   TORCH_CHECK(out.numel() == B * T * H * D && lse.numel() == B * H * T, "attn_fwd: out is [B,T,H,D], lse [B,H,T]");
   TORCH_CHECK(has(doc_start) == has(doc_end), "attn_fwd: doc_start and doc_end go together");
+  uint32_t thr;
+  if (const int64_t* rp = drop_rng(dropout_p, rng, stream, qkv, &thr)) {
+    CHECK_RC(dpe_attn_fwd_drop(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal,
+                               i32_opt(doc_start, B * T, qkv, "attn_fwd: doc_start"),
+                               i32_opt(doc_end, B * T, qkv, "attn_fwd: doc_end"), rp, (uint32_t)stream, thr, cur_stream()),
+             "attn_fwd (dropout: LDS-DMA kernels only)");
+    return {out, lse};
+  }
   CHECK_RC(dpe_attn_fwd(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal,
                         i32_opt(doc_start, B * T, qkv, "attn_fwd: doc_start"),
                         i32_opt(doc_end, B * T, qkv, "attn_fwd: doc_end"), cur_stream()),
@@ -429,7 +489,7 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool ca
 
 Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const Tensor& lse, int64_t H, double scale,
                 bool causal, const c10::optional<Tensor>& dqkv_, const c10::optional<Tensor>& doc_start,
-                const c10::optional<Tensor>& doc_end) {
+                const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng, int64_t stream) {
   CHECK_GPU(qkv); CHECK_BF16(dout); CHECK_CONTIG(dout); CHECK_CONTIG(out);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   Tensor dqkv = has(dqkv_) ? *dqkv_ : at::empty_like(qkv);
@@ -437,6 +497,14 @@ Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const 
   TORCH_CHECK(dqkv.numel() == qkv.numel(), "attn_bwd: dqkv must have qkv's size");
   Tensor delta = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
   TORCH_CHECK(has(doc_start) == has(doc_end), "attn_bwd: doc_start and doc_end go together");
+  uint32_t thr;
+  if (const int64_t* rp = drop_rng(dropout_p, rng, stream, qkv, &thr)) {
+    CHECK_RC(dpe_attn_bwd_drop(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
+                               (float)scale, causal, i32_opt(doc_start, B * T, qkv, "attn_bwd: doc_start"),
+                               i32_opt(doc_end, B * T, qkv, "attn_bwd: doc_end"), rp, (uint32_t)stream, thr, cur_stream()),
+             "attn_bwd (dropout: LDS-DMA kernels only)");
+    return dqkv;
+  }
   CHECK_RC(dpe_attn_bwd(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), nullptr, bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
                         (float)scale, causal, i32_opt(doc_start, B * T, qkv, "attn_bwd: doc_start"),
                         i32_opt(doc_end, B * T, qkv, "attn_bwd: doc_end"), cur_stream()), "attn_bwd");
@@ -511,10 +579,15 @@ void register_ops(pybind11::module& m) {
         }, py::arg("stop"), py::arg("value") = 1, "set a cu_hog stop flag, ordered on the current stream");
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("causal") = true,
         py::arg("out") = py::none(), py::arg("lse") = py::none(), py::arg("doc_start") = py::none(),
-        py::arg("doc_end") = py::none());
+        py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("H"),
         py::arg("scale"), py::arg("causal") = true, py::arg("dqkv") = py::none(), py::arg("doc_start") = py::none(),
-        py::arg("doc_end") = py::none());
+        py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0);
+  m.def("dropout_add", &dropout_add, py::arg("res"), py::arg("y"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,
+        py::arg("out") = py::none(), "fp32 res + dropout(y) (y bf16 or fp32); mask from the device rng state int64[2] (seed, offset) and the stream");
+  m.def("dropout_cast", &dropout_cast, py::arg("g"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,
+        py::arg("out") = py::none(),
+        "bf16 dropout(g) of an fp32 g with dropout_add's mask (its backward)");
   m.def("set_attn_staged", [](bool on) { return dpe_set_attn_staged(on ? 1 : 0) != 0; }, py::arg("on"),
         "attention on the register-staged kernels instead of the LDS-DMA ones (test switch; default off); returns the "
         "previous setting");

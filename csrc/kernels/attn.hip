@@ -312,6 +312,51 @@ DPE_DEVICE void attn_vm_drain() {
   asm volatile("" ::: "memory");
 }
 
+
+// ---- dropout on P (DROP instantiations of the three LDS-DMA kernels)
+// The keep mask is a pure function of (seed, offset, stream, b, h, i, j): P is covered by 4-query x 4-key granules,
+// granule (bh, i/4, j/4) draws r = philox4x32(seed, offset + G, stream) with G = (bh * T/4 + i/4) * T/4 + j/4, and
+// element (i, j) keeps iff byte j%4 of word r[i%4] is >= thr (drop rate thr/256, kept P scaled by 256/(256 - thr)).
+// seed and offset are read from device memory (rng), so a captured step replays with whatever the state holds then.
+// A 4x4 granule is register-contiguous in both layouts: query on the lane and 4 keys per accumulator group (forward,
+// dQ), key on the lane and 4 queries per group (dK/dV).  The four lanes of a quad (4 adjacent queries, or keys)
+// share the same 8 granules per 32x64 wave tile: each lane draws two of them and the words go round by DPP quad
+// permutes (no LDS), 2 Philox calls per lane and tile instead of 8.
+struct AttnDrop {
+  const int64_t* rng;  // device int64[2]: seed, offset
+  uint32_t stream, thr;
+};
+
+template <int CTRL>
+DPE_DEVICE uint32_t quad_perm(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
+}
+
+// 4x4 transpose over the quad: lane s comes with a[j] = word j of ITS granule (s) and leaves with a[j] = word c of
+// granule j (c = the lane's index in the quad).  Two butterfly stages (lane ^ 1, lane ^ 2), two DPP moves each.
+DPE_DEVICE void quad_transpose(uint32_t (&a)[4], int c) {
+  const bool b0 = c & 1, b1 = c & 2;
+  {
+    const uint32_t r0 = quad_perm<0xB1>(b0 ? a[0] : a[1]), r1 = quad_perm<0xB1>(b0 ? a[2] : a[3]);
+    a[0] = b0 ? r0 : a[0]; a[1] = b0 ? a[1] : r0;
+    a[2] = b0 ? r1 : a[2]; a[3] = b0 ? a[3] : r1;
+  }
+  {
+    const uint32_t r0 = quad_perm<0x4E>(b1 ? a[0] : a[2]), r1 = quad_perm<0x4E>(b1 ? a[1] : a[3]);
+    a[0] = b1 ? r0 : a[0]; a[2] = b1 ? a[2] : r0;
+    a[1] = b1 ? r1 : a[1]; a[3] = b1 ? a[3] : r1;
+  }
+}
+
+// Query on the lane (forward, dQ): the lane's 16 keys of accumulator row block r are 4 granules (nt), of which it
+// needs word (query % 4).  Lane c of the quad draws granule nt = c; ctr = offset + G of (row block r, nt = c) in
+// key tile 0, kg = 16 * kt the tile's first key group.
+DPE_DEVICE void drop_words_q(uint32_t (&w)[4], uint64_t seed, uint64_t ctr, uint32_t kg, uint32_t stream, int c) {
+  const u32x4 a = philox4x32(seed, ctr + kg, stream);
+  w[0] = a[0]; w[1] = a[1]; w[2] = a[2]; w[3] = a[3];
+  quad_transpose(w, c);
+}
+DPE_DEVICE bool drop_keep(uint32_t word, int byte, uint32_t thr) { return ((word >> (8 * byte)) & 0xffu) >= thr; }
 //
 // PACKED (documents packed end to end into a row, block-diagonal causal mask): doc_start[b][t] is the row index of
 // the first token of t's document (non-decreasing, <= t), and query i sees key j iff doc_start[b][i] <= j <= i.
@@ -321,10 +366,12 @@ DPE_DEVICE void attn_vm_drain() {
 // max is still -inf (the causal kernel never meets this: key 0 is visible to every query), so a masked element is
 // never given a score: it is left out of the row max and its P is an exact 0 by select, whatever m is.  Values of
 // doc_start only choose tiles (clamped to the causal kernel's walk) and masks, never an address.
-template <bool PACKED>
+// DROP: dropout on P.  The row sum (and lse2) take the undropped bf16 P, O accumulates the dropped fragments and the
+// 256 / (256 - thr) scale is folded into the final 1 / l; a dropped or masked P is an exact 0 by select.
+template <bool PACKED, bool DROP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_fwd_dma_kernel(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse2, int B, int T, int H,
-    float sl2, const int* __restrict__ doc_start) {
+    float sl2, const int* __restrict__ doc_start, AttnDrop dr) {
   constexpr int KB = 2 * AKV * 64, STG = KB + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
@@ -397,6 +444,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});
   const int kd = (q0w + 1) / AKV;
+  // dropout: the counter of the granule this lane draws (key group nt = li & 3) in key tile 0, per row block
+  [[maybe_unused]] uint64_t dseed = 0, dctr[2] = {0, 0};
+  if constexpr (DROP) {
+    const uint64_t n4 = (uint64_t)(T >> 2);
+    dseed = (uint64_t)dr.rng[0];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      dctr[r] = (uint64_t)dr.rng[1] + ((uint64_t)bh * n4 + (uint64_t)((q0w + 16 * r + li) >> 2)) * n4 + (uint64_t)(4 * (li & 3) + g);
+  }
 
   // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask
   auto compute = [&](int kt, const char* s, auto maskc) __attribute__((always_inline)) {
@@ -479,6 +535,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
       pk[r][0] = pack_frag(sc[r][0], sc[r][1]);
       pk[r][1] = pack_frag(sc[r][2], sc[r][3]);
       accl[r] = MFMA(ones, pk[r][1], MFMA(ones, pk[r][0], accl[r]));
+      if constexpr (DROP) {  // l summed the undropped P above; O takes the dropped fragments
+        uint32_t dw[4];
+        drop_words_q(dw, dseed, dctr[r], (uint32_t)kt * (AKV / 4), dr.stream, li & 3);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sc[r][nt][e] = drop_keep(dw[nt], e, dr.thr) ? sc[r][nt][e] : 0.f;
+        pk[r][0] = pack_frag(sc[r][0], sc[r][1]);
+        pk[r][1] = pack_frag(sc[r][2], sc[r][3]);
+      }
     }
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
@@ -518,7 +584,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
   for (int r = 0; r < 2; ++r) {
     const int myq = q0w + 16 * r + li;
     const float l = accl[r][0];  // every row of the all-ones product is the sum over keys for query li
-    const float inv = 1.f / l;
+    const float inv = (DROP ? 256.f / (float)(256u - dr.thr) : 1.f) / l;
     uint16_t* o = out + ((int64_t)(b * T + myq) * H + h) * AD;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
@@ -708,12 +774,15 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
 // first key masks on both bounds.  The tile's 64 doc_start values are staged beside lse / -delta (+256 B per
 // buffer); P of a masked query is 0 by select after the exp2, so an overflowed exp2 of a foreign document's score
 // never reaches dS.
-template <bool PACKED>
+// DROP: P is dropped for dV (the 256 / (256 - thr) scale goes into the final dV), and dS = P (M s dP - delta): the dP
+// chain starts from 0, not -delta, because the mask multiplies dP before the subtraction.  The DROP instantiations need
+// ~300 VGPRs (the mask words and -delta live beside P and dP): one wave per SIMD, no scratch; capped at 256 they spill.
+template <bool PACKED, bool DROP>
 __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
                                                        const float* __restrict__ lse2, const float* __restrict__ delta,
                                                        uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
                                                        float scale, const int* __restrict__ doc_start,
-                                                       const int* __restrict__ doc_end) {
+                                                       const int* __restrict__ doc_end, AttnDrop dr) {
   // per buffer: Qk Qm dOk dOm (8 KB each) + lse, delta (512 B) (+ packed: doc_start, 256 B)
   constexpr int BUF = 4 * 8192 + 512 + (PACKED ? 256 : 0);
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -741,6 +810,17 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
       kf[r][kk] = live ? __builtin_bit_cast(bf16x8, *(const u32x4*)(kb + off)) : bf16x8{};
       vf[r][kk] = live ? __builtin_bit_cast(bf16x8, *(const u32x4*)(vb + off)) : bf16x8{};
     }
+  // dropout: the counter of the granule this lane draws (query group mt = li & 3) in query tile 0, per row block
+  [[maybe_unused]] uint64_t dseed = 0, dn4 = 0, dctr[2] = {0, 0};
+  [[maybe_unused]] float dscale = 1.f;
+  if constexpr (DROP) {
+    dn4 = (uint64_t)(T >> 2);
+    dseed = (uint64_t)dr.rng[0];
+    dscale = 256.f / (float)(256u - dr.thr);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      dctr[r] = (uint64_t)dr.rng[1] + ((uint64_t)bh * dn4 + (uint64_t)(4 * (li & 3) + g)) * dn4 + (uint64_t)((k0w + 16 * r + li) >> 2);
+  }
   // Q / dO of a query tile: LDS-DMA into [Qk | Qm | Ok | Om] (8 KiB each); lse / -delta via registers
   float lv = 0.f;
   [[maybe_unused]] int dsv = 0;
@@ -815,12 +895,28 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
       const float* snd = sl + 64;
       // S[q][key], dP[q][key] - delta[q]: lane = key, rows q = 16mt + 4g + e (the dP chain starts
       // from -delta, so dS = P * dP' needs no subtraction)
+      // dropout: key on the lane, so of each of its 8 granules the lane needs byte (key % 4) of all four words.
+      // Lane c of the quad draws the granule of query group mt = c (per row block) and turns its bytes (word c' :=
+      // byte c' of words 0..3); the quad transpose then leaves dm[r][mt] = the lane's four bytes of granule mt.
+      [[maybe_unused]] uint32_t dm[2][4];
+      if constexpr (DROP) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const u32x4 a = philox4x32(dseed, dctr[r] + (uint64_t)(uint32_t)(qt * (AQ / 4)) * dn4, dr.stream);
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            dm[r][c] = ((a[0] >> (8 * c)) & 0xffu) | (((a[1] >> (8 * c)) & 0xffu) << 8) | (((a[2] >> (8 * c)) & 0xffu) << 16) |
+                       (((a[3] >> (8 * c)) & 0xffu) << 24);
+          quad_transpose(dm[r], li & 3);
+        }
+      }
       f32x4 ps[2][4], dp[2][4];
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
         const bf16x8 q0 = kfrag64(Qk, 16 * mt), q1 = kfrag64(Qk + 4096, 16 * mt);
         const bf16x8 o0 = kfrag64(Ok, 16 * mt), o1 = kfrag64(Ok + 4096, 16 * mt);
-        const f32x4 nd4 = *(const f32x4*)(snd + 16 * mt + 4 * g);
+        f32x4 nd4 = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (!DROP) nd4 = *(const f32x4*)(snd + 16 * mt + 4 * g);
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           ps[r][mt] = MFMA(q1, kf[r][1], MFMA(q0, kf[r][0], (f32x4{0.f, 0.f, 0.f, 0.f})));
@@ -832,6 +928,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
         const f32x4 l4 = *(const f32x4*)(sl + 16 * mt + 4 * g);
         [[maybe_unused]] u32x4 d4;
         if constexpr (MK == 2) d4 = *(const u32x4*)(base + 4 * 8192 + 512 + 4 * (16 * mt + 4 * g));
+        [[maybe_unused]] f32x4 ndd;
+        if constexpr (DROP) ndd = *(const f32x4*)(snd + 16 * mt + 4 * g);
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -843,8 +941,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
               const int key = k0w + 16 * r + li;
               p = ((key > qt * AQ + 16 * mt + 4 * g + e) | ((int)d4[e] > key)) ? 0.f : p;
             }
-            ps[r][mt][e] = p;                        // P
-            dp[r][mt][e] = p * dp[r][mt][e];  // dS (unscaled)
+            if constexpr (DROP) {
+              const bool keep = drop_keep(dm[r][mt], e, dr.thr);
+              ps[r][mt][e] = keep ? p : 0.f;                                   // P o M (s in the final dV)
+              dp[r][mt][e] = p * fmaf(dp[r][mt][e], keep ? dscale : 0.f, ndd[e]);  // dS = P (M s dP - delta)
+            } else {
+              ps[r][mt][e] = p;                        // P
+              dp[r][mt][e] = p * dp[r][mt][e];  // dS (unscaled)
+            }
           }
       }
       // dV^T += dO^T . P ; dK^T += Q^T . dS   (k = q, permuted order matches the accumulators)
@@ -899,6 +1003,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
       u32x2 a, c;
       a[0] = pack_bf2(dk[r][d][0] * scale, dk[r][d][1] * scale);
       a[1] = pack_bf2(dk[r][d][2] * scale, dk[r][d][3] * scale);
+      if constexpr (DROP) dv[r][d] *= dscale;
       c[0] = pack_bf2(dv[r][d][0], dv[r][d][1]);
       c[1] = pack_bf2(dv[r][d][2], dv[r][d][3]);
       *(u32x2*)(dkb + 16 * d + 4 * g) = a;
@@ -1058,12 +1163,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const uint16_t* __rest
 // PACKED: the forward's tile walk (attn_fwd_dma_kernel) -- the workgroup starts at its first query's document, a
 // wave skips the tiles before its own, and a tile that crosses a document start of the wave masks on both bounds;
 // P of a masked key is 0 by select after the exp2, as for the causal mask.
-template <bool PACKED>
+// DROP: dS = P (M s dP - delta) with the forward's mask words; the dP chain starts from 0.
+template <bool PACKED, bool DROP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAVES))) void attn_bwd_dq_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o,
                                                           const uint16_t* __restrict__ dout,
                                                           const float* __restrict__ lse2, float* __restrict__ delta,
                                                           uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
-                                                          float scale, const int* __restrict__ doc_start) {
+                                                          float scale, const int* __restrict__ doc_start, AttnDrop dr) {
   // per buffer: K (two d-halves, K-contig) 8K | V (same) 8K | K permuted-row image 8K
   constexpr int KI = 0, VI = 2 * AKV * 64, KP = 4 * AKV * 64, STG = KP + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
@@ -1122,6 +1228,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
   }
 
   // the sequence's qkv rows from K of head h on: one buffer resource, tile advance in soffset
+  // dropout: the forward's counters (attn_fwd_dma_kernel)
+  [[maybe_unused]] uint64_t dseed = 0, dctr[2] = {0, 0};
+  [[maybe_unused]] float dscale = 1.f;
+  if constexpr (DROP) {
+    const uint64_t n4 = (uint64_t)(T >> 2);
+    dseed = (uint64_t)dr.rng[0];
+    dscale = 256.f / (float)(256u - dr.thr);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+      dctr[r] = (uint64_t)dr.rng[1] + ((uint64_t)bh * n4 + (uint64_t)((q0w + 16 * r + li) >> 2)) * n4 + (uint64_t)(4 * (li & 3) + g);
+  }
   const __amdgpu_buffer_rsrc_t rkv =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(kb), (short)0, (int)(T * RS * 2), 0x00020000);
   uint32_t voff[6];  // piece w + 4 i of the 24 KiB image set: [K halves | V halves | K permuted-row]
@@ -1172,13 +1289,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           sc[r][nt] = MFMA(k1, qf[r][1], MFMA(k0, qf[r][0], (f32x4{0.f, 0.f, 0.f, 0.f})));
-          dp[r][nt] = MFMA(v1, of[r][1], MFMA(v0, of[r][0], (f32x4{ndl[r], ndl[r], ndl[r], ndl[r]})));
+          const float c0 = DROP ? 0.f : ndl[r];
+          dp[r][nt] = MFMA(v1, of[r][1], MFMA(v0, of[r][0], (f32x4{c0, c0, c0, c0})));
         }
       }
       bf16x8 dd[2][2];
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int myq = q0w + 16 * r + li;
+        [[maybe_unused]] uint32_t dw[4];
+        if constexpr (DROP) drop_words_q(dw, dseed, dctr[r], (uint32_t)kt * (AKV / 4), dr.stream, li & 3);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -1190,7 +1310,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
               const int key = kt * AKV + 16 * nt + 4 * g + e;
               p = ((key > myq) | (key < ds[r])) ? 0.f : p;
             }
-            dp[r][nt][e] = p * dp[r][nt][e];  // dS^T (unscaled); dP^T started from -delta
+            if constexpr (DROP)  // dS^T = P (M s dP^T - delta); dP^T started from 0
+              dp[r][nt][e] = p * fmaf(dp[r][nt][e], drop_keep(dw[nt], e, dr.thr) ? dscale : 0.f, ndl[r]);
+            else
+              dp[r][nt][e] = p * dp[r][nt][e];  // dS^T (unscaled); dP^T started from -delta
           }
         dd[r][0] = pack_frag(dp[r][0], dp[r][1]);
         dd[r][1] = pack_frag(dp[r][2], dp[r][3]);
@@ -1256,14 +1379,15 @@ extern "C" int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int 
   const dim3 grid(B * H * ((T + FQ - 1) / FQ));
   if (doc_start) {
     if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
-    hipLaunchKernelGGL(attn_fwd_dma_kernel<true>, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start);
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, false>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, AttnDrop{});
     return 0;
   }
 #ifdef DPE_ATTN_FWD_STAGED
   hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
 #else
   if (dma)
-    hipLaunchKernelGGL(attn_fwd_dma_kernel<false>, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, (const int*)nullptr);
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<false, false>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, (const int*)nullptr,
+                       AttnDrop{});
   else
     hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
 #endif
@@ -1282,10 +1406,10 @@ extern "C" int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint
   // dQ first: it also writes delta = rowsum(dO * O), which the dK/dV kernel reads
   if (doc_start) {
     if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
-    hipLaunchKernelGGL(attn_bwd_dq_dma_kernel<true>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2,
-                       scale, doc_start);
-    hipLaunchKernelGGL(attn_bwd_dma_kernel<true>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       doc_start, doc_end);
+    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<true, false>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
+                       sl2, scale, doc_start, AttnDrop{});
+    hipLaunchKernelGGL((attn_bwd_dma_kernel<true, false>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
+                       doc_start, doc_end, AttnDrop{});
     return 0;
   }
 #ifdef DPE_ATTN_BWD_STAGED
@@ -1294,14 +1418,59 @@ extern "C" int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint
   (void)dma;
 #else
   if (dma) {
-    hipLaunchKernelGGL(attn_bwd_dq_dma_kernel<false>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2,
-                       scale, (const int*)nullptr);
-    hipLaunchKernelGGL(attn_bwd_dma_kernel<false>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       (const int*)nullptr, (const int*)nullptr);
+    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, false>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
+                       sl2, scale, (const int*)nullptr, AttnDrop{});
+    hipLaunchKernelGGL((attn_bwd_dma_kernel<false, false>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
+                       (const int*)nullptr, (const int*)nullptr, AttnDrop{});
   } else {
     hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2, scale);
     hipLaunchKernelGGL(attn_bwd_kernel, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale);
   }
 #endif
+  return 0;
+}
+
+// Dropout on P (thr in [1, 255]: drop rate thr / 256; rng = device int64[2] (seed, offset); stream = the call site).
+// LDS-DMA kernels only: a shape or switch that would take the register-staged kernels is an error, as for packed
+// documents.  doc_start / doc_end as above (null = plain causal).
+extern "C" int dpe_attn_fwd_drop(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale,
+                                 int causal, const int32_t* doc_start, const int32_t* doc_end, const int64_t* rng,
+                                 uint32_t stream, uint32_t thr, hipStream_t st) {
+  if (D != AD || T % AKV != 0 || !causal || !rng || thr < 1 || thr > 255) return -1;
+  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
+  if ((doc_start != nullptr) != (doc_end != nullptr)) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 grid(B * H * ((T + FQ - 1) / FQ));
+  const AttnDrop dr{rng, stream, thr};
+  if (doc_start)
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, true>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, dr);
+  else
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<false, true>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2,
+                       (const int*)nullptr, dr);
+  return 0;
+}
+
+extern "C" int dpe_attn_bwd_drop(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
+                                 float* delta, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal,
+                                 const int32_t* doc_start, const int32_t* doc_end, const int64_t* rng, uint32_t stream,
+                                 uint32_t thr, hipStream_t st) {
+  if (D != AD || T % AKV != 0 || !causal || !rng || thr < 1 || thr > 255) return -1;
+  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
+  if ((doc_start != nullptr) != (doc_end != nullptr)) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 gq(B * H * ((T + FQ - 1) / FQ)), gk(B * H * ((T + BKW - 1) / BKW));
+  const AttnDrop dr{rng, stream, thr};
+  // dQ first: it also writes delta = rowsum(dO * O) (O is the dropped output), which the dK/dV kernel reads
+  if (doc_start) {
+    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<true, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
+                       sl2, scale, doc_start, dr);
+    hipLaunchKernelGGL((attn_bwd_dma_kernel<true, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
+                       doc_start, doc_end, dr);
+  } else {
+    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
+                       sl2, scale, (const int*)nullptr, dr);
+    hipLaunchKernelGGL((attn_bwd_dma_kernel<false, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
+                       (const int*)nullptr, (const int*)nullptr, dr);
+  }
   return 0;
 }

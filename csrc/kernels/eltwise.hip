@@ -115,6 +115,73 @@ __global__ __launch_bounds__(ET) void dropout_kernel(const T* __restrict__ x, T*
   }
 }
 
+// Residual / embedding dropout with the RNG state on the device: rng = int64[2] (seed, offset), read by the kernel, so
+// a captured step draws a new mask on every replay.  dropout_kernel's rule with a call-site stream in counter_lo:
+// element n keeps iff philox4x32(seed, offset + n/4, stream)[n % 4] >= p * 2^32; scale 1/(1-p).  Exact grids, one
+// thread per 8 elements (two Philox granules, 16-B accesses); the last thread's partial group goes element by element.
+DPE_DEVICE uint32_t drop_thr32(float p) { return (uint32_t)fminf(p * 4294967296.f, 4294967295.f); }
+
+// out = res + mask(y) * s   (fp32 res / out; y bf16 or fp32)
+template <typename T>
+__global__ __launch_bounds__(ET) void dropout_add_kernel(const float* __restrict__ res, const T* __restrict__ y,
+                                                         float* __restrict__ out, int64_t n, float p,
+                                                         const int64_t* __restrict__ rng, uint32_t stream) {
+  const uint32_t thr = drop_thr32(p);
+  const float scale = 1.f / (1.f - p);
+  const uint64_t seed = (uint64_t)rng[0], offset = (uint64_t)rng[1];
+  const int64_t i = blockIdx.x * (int64_t)ET + threadIdx.x;  // group of 8 elements
+  if (i * 8 >= n) return;
+  const u32x4 r0 = philox4x32(seed, offset + (uint64_t)(2 * i), stream), r1 = philox4x32(seed, offset + (uint64_t)(2 * i + 1), stream);
+  const uint32_t rr[8] = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
+  if (i * 8 + 8 <= n) {
+    float f[8];
+    if constexpr (sizeof(T) == 2) {
+      unpack8(*(const u32x4*)(y + i * 8), f);
+    } else {
+      const f32x4 a = *(const f32x4*)(y + i * 8), b = *(const f32x4*)(y + i * 8 + 4);
+      f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
+    }
+    const f32x4 ra = *(const f32x4*)(res + i * 8), rb = *(const f32x4*)(res + i * 8 + 4);
+    f32x4 oa, ob;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      oa[e] = ra[e] + (rr[e] >= thr ? f[e] * scale : 0.f);
+      ob[e] = rb[e] + (rr[4 + e] >= thr ? f[4 + e] * scale : 0.f);
+    }
+    *(f32x4*)(out + i * 8) = oa;
+    *(f32x4*)(out + i * 8 + 4) = ob;
+  } else {
+    for (int e = 0; e < 8 && i * 8 + e < n; ++e) {
+      const int64_t j = i * 8 + e;
+      out[j] = res[j] + (rr[e] >= thr ? lf<T>(y, j) * scale : 0.f);
+    }
+  }
+}
+
+// out (bf16) = mask(g) * s   (fp32 g): the backward's masked cast
+__global__ __launch_bounds__(ET) void dropout_cast_kernel(const float* __restrict__ g, uint16_t* __restrict__ out, int64_t n,
+                                                          float p, const int64_t* __restrict__ rng, uint32_t stream) {
+  const uint32_t thr = drop_thr32(p);
+  const float scale = 1.f / (1.f - p);
+  const uint64_t seed = (uint64_t)rng[0], offset = (uint64_t)rng[1];
+  const int64_t i = blockIdx.x * (int64_t)ET + threadIdx.x;  // group of 8 elements
+  if (i * 8 >= n) return;
+  const u32x4 r0 = philox4x32(seed, offset + (uint64_t)(2 * i), stream), r1 = philox4x32(seed, offset + (uint64_t)(2 * i + 1), stream);
+  const uint32_t rr[8] = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
+  if (i * 8 + 8 <= n) {
+    const f32x4 a = *(const f32x4*)(g + i * 8), b = *(const f32x4*)(g + i * 8 + 4);
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      f[e] = rr[e] >= thr ? a[e] * scale : 0.f;
+      f[4 + e] = rr[4 + e] >= thr ? b[e] * scale : 0.f;
+    }
+    *(u32x4*)(out + i * 8) = pack8(f);
+  } else {
+    for (int e = 0; e < 8 && i * 8 + e < n; ++e) out[i * 8 + e] = f2bf(rr[e] >= thr ? g[i * 8 + e] * scale : 0.f);
+  }
+}
+
 // --------------------------------------------------------------- residual
 template <typename T>
 __global__ __launch_bounds__(ET) void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out,
@@ -354,6 +421,27 @@ extern "C" int dpe_dropout(const void* x, void* y, int64_t n, float p, uint64_t 
   else
     hipLaunchKernelGGL((dropout_kernel<float>), dim3(egrid((n + 3) / 4)), dim3(ET), 0, st, (const float*)x, (float*)y, n, p,
                        seed, offset);
+  return 0;
+}
+// res, y, out (dropout_add) and g, out (dropout_cast) 16-B aligned; p in [0, 1)
+extern "C" int dpe_dropout_add(const float* res, const void* y, int y_bf16, float* out, int64_t n, float p,
+                               const int64_t* rng, uint32_t stream, hipStream_t st) {
+  if (!(p >= 0.f && p < 1.f) || !rng || n < 0 || cdiv(n, 8 * ET) > 0x7fffffffLL) return -1;
+  if ((uintptr_t)res % 16 || (uintptr_t)y % 16 || (uintptr_t)out % 16) return -1;
+  if (n == 0) return 0;
+  const dim3 grid((unsigned)cdiv(n, 8 * ET));
+  if (y_bf16)
+    hipLaunchKernelGGL((dropout_add_kernel<uint16_t>), grid, dim3(ET), 0, st, res, (const uint16_t*)y, out, n, p, rng, stream);
+  else
+    hipLaunchKernelGGL((dropout_add_kernel<float>), grid, dim3(ET), 0, st, res, (const float*)y, out, n, p, rng, stream);
+  return 0;
+}
+extern "C" int dpe_dropout_cast(const float* g, uint16_t* out, int64_t n, float p, const int64_t* rng, uint32_t stream,
+                                hipStream_t st) {
+  if (!(p >= 0.f && p < 1.f) || !rng || n < 0 || cdiv(n, 8 * ET) > 0x7fffffffLL) return -1;
+  if ((uintptr_t)g % 16 || (uintptr_t)out % 16) return -1;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(dropout_cast_kernel, dim3((unsigned)cdiv(n, 8 * ET)), dim3(ET), 0, st, g, out, n, p, rng, stream);
   return 0;
 }
 extern "C" int dpe_add(const void* a, const void* b, void* out, int64_t n, float alpha, int bf16, hipStream_t st) {

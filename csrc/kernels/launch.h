@@ -92,6 +92,10 @@ int dpe_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t st);
 int dpe_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t st);
 int dpe_act(const void* a, const void* b, void* out, int64_t n, int op, int bf16, hipStream_t st);
 int dpe_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, uint64_t offset, int bf16, hipStream_t st);
+// rng = device int64[2] (seed, offset); element n keeps iff philox4x32(seed, offset + n/4, stream)[n % 4] >= p * 2^32
+int dpe_dropout_add(const float* res, const void* y, int y_bf16, float* out, int64_t n, float p, const int64_t* rng,
+                    uint32_t stream, hipStream_t st);
+int dpe_dropout_cast(const float* g, uint16_t* out, int64_t n, float p, const int64_t* rng, uint32_t stream, hipStream_t st);
 int dpe_add(const void* a, const void* b, void* out, int64_t n, float alpha, int bf16, hipStream_t st);
 int dpe_colsum(const void* dy, int64_t M, int N, int64_t ld, float* db, int accumulate, int bf16, hipStream_t st);
 int dpe_nchw_to_s2d(const float* x, uint16_t* y, int N, int C, int H, int W, hipStream_t st);
@@ -146,6 +150,13 @@ int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout,
                  float* dq_acc, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, const int32_t* doc_start,
                  const int32_t* doc_end, hipStream_t st);
 int dpe_set_attn_staged(int on);
+// dropout on P (LDS-DMA kernels only): rng = device int64[2] (seed, offset), stream = call site, drop rate thr / 256
+int dpe_attn_fwd_drop(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int causal,
+                      const int32_t* doc_start, const int32_t* doc_end, const int64_t* rng, uint32_t stream, uint32_t thr,
+                      hipStream_t st);
+int dpe_attn_bwd_drop(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
+                      uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, const int32_t* doc_start,
+                      const int32_t* doc_end, const int64_t* rng, uint32_t stream, uint32_t thr, hipStream_t st);
 // ---- gemm_f32.hip
 int dpe_gemm_f32(const float* A, const float* B, float* C, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,
                  int64_t ldc, int M, int N, int K, const float* bias, float alpha, int relu, float drop_p,

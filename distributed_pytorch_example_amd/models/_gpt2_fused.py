@@ -22,6 +22,10 @@ backward (g = dL/dy fp32, gb its bf16 copy)
     dW_qkv += dqkv^T h1 ; db_qkv ; dh1 = dqkv W_qkv
     g1, g1b = g2 + LN1'(dh1)        -> returned; g1b handed to the previous block
 
+With dropout (``drop = (p, rng snapshot, first stream)``, training with cfg.dropout > 0): attention drops P in
+its kernels, both projections write bf16 and ``dropout_add`` forms ``x + dropout(proj)``; in backward the bf16
+inputs of the two projections' gradients are masked casts (``dropout_cast``) of g and g2, never the carried copy.
+
 The bf16 copy of the returned gradient is passed to the next backward node
 (the previous block) through ``_carry``: it is used only if that node receives
 exactly the tensor this node returned (same storage, shape and version), else
@@ -187,7 +191,7 @@ def block_params(blk):
 
 class BlockFn(Function):
     @staticmethod
-    def forward(ctx, x, blk, doc, *params):
+    def forward(ctx, x, blk, doc, drop, *params):
         C = ext()
         B, T, D = x.shape
         H = blk.n_head
@@ -201,19 +205,33 @@ class BlockFn(Function):
         h1, m1, r1 = C.layernorm_fwd(x, blk.ln_1.weight.detach(), opt(blk.ln_1.bias), blk.ln_1.eps)
         qkv = C.linear_fwd(h1, shadow(blk.c_attn.weight), opt(blk.c_attn.bias), 0, False, None, None)
         qkv5 = qkv.view(B, T, 3, H, hd)
-        if doc is None:
+        if drop is not None:
+            # dropout (p, rng snapshot, first stream): on P inside the attention kernels; the projections write
+            # bf16 and dropout_add forms the fp32 x + dropout(proj) (no fp32-residual GEMM epilogue here)
+            dp, rng, ds0 = drop
+            a, lse = C.attn_fwd(qkv5, H, scale, True, doc_start=None if doc is None else doc[0],
+                                doc_end=None if doc is None else doc[1], dropout_p=dp, rng=rng, stream=ds0)
+        elif doc is None:
             a, lse = C.attn_fwd(qkv5, H, scale, True)
         else:  # packed documents: (doc_start, doc_end, pos) of Fx.doc_bounds
             a, lse = C.attn_fwd(qkv5, H, scale, True, doc_start=doc[0], doc_end=doc[1])
         a = a.view(B, T, D)
-        x2 = C.linear_fwd(a, shadow(blk.attn_proj.weight), opt(blk.attn_proj.bias), 0, True, x, None)
+        if drop is not None:
+            pa = C.linear_fwd(a, shadow(blk.attn_proj.weight), opt(blk.attn_proj.bias), 0, False, None, None)
+            x2 = C.dropout_add(x, pa, dp, rng, ds0 + 1)
+        else:
+            x2 = C.linear_fwd(a, shadow(blk.attn_proj.weight), opt(blk.attn_proj.bias), 0, True, x, None)
         h2, m2, r2 = C.layernorm_fwd(x2, blk.ln_2.weight.detach(), opt(blk.ln_2.bias), blk.ln_2.eps)
         # GELU in the GEMM epilogue; the pre-activation v is written alongside for the backward
         v = torch.empty((B, T, blk.c_fc.weight.shape[0]), device=x.device, dtype=torch.bfloat16)
         u = C.linear_fwd(h2, shadow(blk.c_fc.weight), opt(blk.c_fc.bias), 2, False, None, None, v)
-        y = C.linear_fwd(u, shadow(blk.mlp_proj.weight), opt(blk.mlp_proj.bias), 0, True, x2, None)
+        if drop is not None:
+            pm = C.linear_fwd(u, shadow(blk.mlp_proj.weight), opt(blk.mlp_proj.bias), 0, False, None, None)
+            y = C.dropout_add(x2, pm, dp, rng, ds0 + 2)
+        else:
+            y = C.linear_fwd(u, shadow(blk.mlp_proj.weight), opt(blk.mlp_proj.bias), 0, True, x2, None)
         ctx.save_for_backward(x, h1, m1, r1, qkv5, a, lse, x2, h2, m2, r2, v, u)
-        ctx.blk, ctx.scale, ctx.doc = blk, scale, doc
+        ctx.blk, ctx.scale, ctx.doc, ctx.drop = blk, scale, doc, drop
         for p in params:
             note_use(p)
         return y
@@ -224,7 +242,14 @@ class BlockFn(Function):
         x, h1, m1, r1, qkv5, a, lse, x2, h2, m2, r2, v, u = ctx.saved_tensors
         blk = ctx.blk
         g = g.contiguous()
-        gb = _bf16_of(g)
+        drop = ctx.drop
+        if drop is None:
+            gb = _bf16_of(g)
+        else:
+            # a mask stands between the incoming gradient and mlp_proj: its bf16 form is the masked cast, not the
+            # plain copy the next block carried over
+            _carry[0] = None
+            gb = C.dropout_cast(g, drop[0], drop[1], drop[2] + 2)
         grads = {}
         T = g.numel() // g.shape[-1]
         group = _WG_GROUP > 0 and T % 64 == 0 and g.shape[-1] % 8 == 0
@@ -285,9 +310,15 @@ class BlockFn(Function):
         dv = linear_bwd(blk.mlp_proj, gb, u, gelu_in=v)  # GELU backward in the data-grad epilogue
         dh2 = linear_bwd(blk.c_fc, dv, h2)
         g2, g2b = ln_bwd(blk.ln_2, dh2, x2, m2, r2, g)
+        if drop is not None:  # likewise for attn_proj: the masked cast of the stream gradient
+            g2b = C.dropout_cast(g2, drop[0], drop[1], drop[2] + 1)
         da = linear_bwd(blk.attn_proj, g2b, a)
         a4 = a.view(qkv5.shape[0], qkv5.shape[1], qkv5.shape[3], qkv5.shape[4])
-        if ctx.doc is None:
+        if drop is not None:
+            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True,
+                              doc_start=None if ctx.doc is None else ctx.doc[0],
+                              doc_end=None if ctx.doc is None else ctx.doc[1], dropout_p=drop[0], rng=drop[1], stream=drop[2])
+        elif ctx.doc is None:
             dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True)
         else:
             dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True, doc_start=ctx.doc[0], doc_end=ctx.doc[1])
@@ -302,9 +333,10 @@ class BlockFn(Function):
             flush_wgrad_queue()  # every _WG_GROUP layers, and always at the first block (end of backward)
         _carry[0] = (g1, g1b, g1._version)
         pgrads = [grads.get(id(p)) for p in block_params(blk)]
-        return (g1, None, None, *pgrads)
+        return (g1, None, None, None, *pgrads)
 
 
-def block_forward(blk, x, doc=None):
-    return BlockFn.apply(x, blk, doc, *block_params(blk))
+def block_forward(blk, x, doc=None, drop=None):
+    """``drop``: None, or (p, rng snapshot, first stream) for a training forward with dropout (Block.forward)."""
+    return BlockFn.apply(x, blk, doc, drop, *block_params(blk))
 

@@ -65,14 +65,27 @@ class Block(nn.Module):
         for lin in (self.c_attn, self.attn_proj, self.c_fc, self.mlp_proj):
             lin.weight._dpe_overwrite_ok = True
 
-    def forward(self, x, doc=None):
-        """``doc``: the (doc_start, doc_end, pos) of Fx.doc_bounds for packed documents, None for one per row."""
+    def forward(self, x, doc=None, drop=None):
+        """``doc``: the (doc_start, doc_end, pos) of Fx.doc_bounds for packed documents, None for one per row.
+        ``drop``: None, or (p, rng, stream) for a training forward with dropout -- p the rate, rng the forward's
+        DropoutState snapshot (None off the GPU), stream the layer's first call-site id (attention; + 1 the
+        attention residual, + 2 the MLP residual)."""
         # (the fused block calls the attention kernels directly: only for the shapes they take)
         if (x.is_cuda and self.fused and torch.is_grad_enabled()
                 and Fx.attn_kernel_ok(x.shape[1], x.shape[2] // self.n_head)):
             from ._gpt2_fused import block_forward  # hand-scheduled fwd/bwd, one autograd node
 
-            return block_forward(self, x, doc)
+            return block_forward(self, x, doc) if drop is None else block_forward(self, x, doc, drop)
+        if drop is not None:
+            # dropout on P and on both projections' outputs: the projection GEMMs write bf16 (no fp32-residual
+            # epilogue) and dropout_add forms x + dropout(proj)
+            p, rng, stream = drop
+            h = self.ln_1(x)
+            a = Fx.causal_attention(self.c_attn(h), self.n_head, doc, dropout_p=p, rng=rng, stream=stream)
+            x = Fx.dropout_add(x, self.attn_proj(a), p, rng, stream + 1)
+            h = self.ln_2(x)
+            u = Fx.gelu(self.c_fc(h))
+            return Fx.dropout_add(x, self.mlp_proj(u), p, rng, stream + 2)
         h = self.ln_1(x)
         qkv = self.c_attn(h)
         a = Fx.causal_attention(qkv, self.n_head) if doc is None else Fx.causal_attention(qkv, self.n_head, doc)
@@ -124,7 +137,9 @@ class GPT2(nn.Module):
             from ._gpt2_fused import reset_wgrad_queue
 
             reset_wgrad_queue()
-        if doc_start is None:
+        if self.training and self.cfg.dropout > 0.0:
+            x = self._forward_dropout(idx, doc_start)
+        elif doc_start is None:
             x = Fx.embedding(idx, self.wte, self.wpe[:T] if not idx.is_cuda else self.wpe)
             for blk in self.h:
                 x = blk(x)
@@ -138,6 +153,32 @@ class GPT2(nn.Module):
         if targets is not None:
             return Fx.lm_head_ce(x, self.wte, targets, label_smoothing=self.cfg.label_smoothing, z_loss=self.cfg.z_loss)
         return Fx.lm_head(x, self.wte)
+
+    def _forward_dropout(self, idx, doc_start):
+        """The blocks' input and output in training mode with cfg.dropout > 0: dropout on the embedding sum, on the
+        attention probabilities and on both projections' outputs before the residual add.  One snapshot of the
+        device-side RNG state serves the whole forward and its backward; the live state then advances once, by
+        the largest counter range any call of the step uses.  Call sites differ in their stream: embedding 0,
+        layer l attention 1 + 3l, attention residual 2 + 3l, MLP residual 3 + 3l."""
+        B, T = idx.shape
+        p = float(self.cfg.dropout)
+        assert 0.0 < p < 1.0, "dropout must be in [0, 1)"
+        rng = None
+        if idx.is_cuda:
+            st = Fx.dropout_state(idx.device)
+            rng = st.snapshot()
+            st.advance(max(B * self.cfg.n_head * ((T + 3) // 4) ** 2, (B * T * self.cfg.n_embd + 3) // 4))
+        doc = None
+        if doc_start is None:
+            x = Fx.embedding(idx, self.wte, self.wpe[:T] if not idx.is_cuda else self.wpe)
+        else:
+            assert doc_start.shape == idx.shape, "doc_start must have idx's shape"
+            doc = Fx.doc_bounds(doc_start)
+            x = Fx.embedding(idx, self.wte, self.wpe, doc[2])
+        x = Fx.dropout_rng(x, p, rng, 0)
+        for l, blk in enumerate(self.h):
+            x = blk(x, doc, (p, rng, 1 + 3 * l))
+        return x
 
     def num_params(self) -> int:
         return sum(p.numel() for p in self.parameters())

@@ -190,6 +190,133 @@ def dropout(x, p: float, training: bool):
     return _DropoutFn.apply(x, p)
 
 
+# ---- dropout whose per-step state lives on the device (GPT-2: attention, residual and embedding dropout)
+# _RNG above advances a Python integer that is baked into kernel arguments, so a captured step would replay one mask
+# for ever.  Here (seed, offset) is a device int64[2] tensor that the kernels read; advancing it is one in-place
+# device op, which a graph captures and replays like the optimizer's device-side lr and step counters.
+class DropoutState:
+    """The dropout RNG state of one device.  ``snapshot()`` is taken once per forward and handed to every kernel
+    of that forward and to its backward (autograd nodes save the snapshot, so another forward in between does not
+    change the masks the backward regenerates); ``advance(stride)`` then moves the live state past the counters
+    that forward can use.  Call sites are told apart by their ``stream`` (Philox counter_lo), not by the offset."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.state = None
+
+    @staticmethod
+    def default_seed() -> int:
+        """torch.initial_seed() mixed with the process rank: DDP ranks draw different masks."""
+        import os
+
+        rank = 0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank()
+        else:
+            rank = int(os.environ.get("RANK", "0") or 0)
+        return (int(torch.initial_seed()) + 0x9E3779B97F4A7C15 * (rank + 1)) & 0x7FFFFFFFFFFFFFFF
+
+    def manual_seed(self, seed: int, offset: int = 0) -> "DropoutState":
+        """(Re)start the state at ``(seed, offset)``; in place once the tensor exists, so captured graphs follow."""
+        new = torch.tensor([int(seed) & 0x7FFFFFFFFFFFFFFF, int(offset)], dtype=torch.int64)
+        if self.state is None:
+            self.state = new.to(self.device)
+        else:
+            self.state.copy_(new)
+        return self
+
+    def tensor(self) -> torch.Tensor:
+        if self.state is None:
+            self.manual_seed(self.default_seed())
+        return self.state
+
+    def advance(self, stride: int) -> None:
+        """offset += stride: one in-place device op (capturable)."""
+        self.tensor()[1:].add_(int(stride))
+
+    def snapshot(self) -> torch.Tensor:
+        """A fresh device copy of (seed, offset) for one forward and its backward."""
+        return self.tensor().clone()
+
+
+_dropout_states: dict = {}
+
+
+def dropout_state(device) -> DropoutState:
+    """The DropoutState of ``device`` (created on first use, seeded by DropoutState.default_seed())."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    st = _dropout_states.get(device)
+    if st is None:
+        st = _dropout_states[device] = DropoutState(device)
+    return st
+
+
+def manual_seed_dropout(seed: int, device=None, offset: int = 0) -> None:
+    """Reseed the device-side dropout state (of ``device``; default: every state created so far, and cuda's current
+    device when there is one)."""
+    if device is not None:
+        dropout_state(device).manual_seed(seed, offset)
+        return
+    if torch.cuda.is_available():
+        dropout_state("cuda")
+    for st in _dropout_states.values():
+        st.manual_seed(seed, offset)
+
+
+def attn_dropout_threshold(p: float) -> int:
+    """The attention kernels compare one byte of Philox output per element of P: an element is dropped iff its
+    byte is below thr = clamp(round(256 p), 1, 255)."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout p must be in [0, 1), got {p}")
+    return min(255, max(1, int(math.floor(256.0 * p + 0.5))))
+
+
+def attn_dropout_rate(p: float) -> float:
+    """The rate the attention kernels apply for a requested ``p`` > 0: thr / 256 (8-bit quantisation; kept
+    probabilities are scaled by 256 / (256 - thr), the inverse of this rate's keep probability, so the expectation
+    is exact).  0 stays 0."""
+    return 0.0 if p == 0.0 else attn_dropout_threshold(p) / 256.0
+
+
+class _DropoutAddFn(Function):
+    """res (fp32) + dropout(y): mask from the device state ``rng`` and ``stream``, regenerated in backward."""
+
+    @staticmethod
+    def forward(ctx, res, y, p: float, rng, stream: int):
+        ctx.p, ctx.rng, ctx.stream, ctx.ydtype = p, rng, stream, y.dtype
+        return ext().dropout_add(res.contiguous(), y.contiguous(), p, rng, stream)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        gy = None
+        if ctx.needs_input_grad[1]:
+            if ctx.ydtype == torch.bfloat16:
+                gy = ext().dropout_cast(g, ctx.p, ctx.rng, ctx.stream)
+            else:
+                gy = ext().dropout_add(torch.zeros_like(g), g, ctx.p, ctx.rng, ctx.stream)
+        return g, gy, None, None, None
+
+
+def dropout_add(res, y, p: float, rng=None, stream: int = 0):
+    """res + dropout(y) in training (fp32 residual stream ``res``; ``y`` bf16 or fp32).  On the GPU ``rng`` is the
+    forward's DropoutState snapshot and ``stream`` the call site; off it torch's generator draws the mask."""
+    if not res.is_cuda:
+        return res + F.dropout(y.float(), p, True)
+    if rng is None:
+        raise ValueError("dropout_add on the GPU needs the forward's rng snapshot")
+    return _DropoutAddFn.apply(res.float(), y, p, rng, stream)
+
+
+def dropout_rng(x, p: float, rng=None, stream: int = 0):
+    """dropout(x) of an fp32 ``x`` with the device-side state (dropout_add onto zeros)."""
+    if not x.is_cuda:
+        return F.dropout(x, p, True)
+    return dropout_add(torch.zeros_like(x, dtype=torch.float32), x, p, rng, stream)
+
+
 # ====================================================================== Conv
 def _conv_out(h, k, s, p, d):
     return (h + 2 * p - d * (k - 1) - 1) // s + 1
@@ -722,8 +849,13 @@ def check_doc_start(doc_start) -> None:
 
 class _AttnFn(Function):
     @staticmethod
-    def forward(ctx, qkv, H: int, scale: float, doc_start=None, doc_end=None):
-        if doc_start is None:
+    def forward(ctx, qkv, H: int, scale: float, doc_start=None, doc_end=None, dropout_p: float = 0.0, rng=None,
+                stream: int = 0):
+        ctx.drop = None
+        if dropout_p > 0.0:  # dropout on P inside the kernels; rng is the forward's snapshot, kept for backward
+            ctx.drop = dict(dropout_p=dropout_p, rng=rng, stream=stream)
+            out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True, doc_start=doc_start, doc_end=doc_end, **ctx.drop)
+        elif doc_start is None:
             out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True)
         else:
             out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True, doc_start=doc_start, doc_end=doc_end)
@@ -735,12 +867,15 @@ class _AttnFn(Function):
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
         ds, de = ctx.doc
-        if ds is None:
+        if ctx.drop is not None:
+            dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True,
+                                  doc_start=ds, doc_end=de, **ctx.drop)
+        elif ds is None:
             dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True)
         else:
             dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True,
                                   doc_start=ds, doc_end=de)
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 def attn_kernel_ok(T: int, D: int) -> bool:
@@ -748,10 +883,11 @@ def attn_kernel_ok(T: int, D: int) -> bool:
     return D == 64 and T % 64 == 0
 
 
-def _causal_attention_torch(qkv5, scale: float, doc_start=None):
-    """Shapes outside the kernels' range (and every packed-document call off the GPU): explicit masked
+def _causal_attention_torch(qkv5, scale: float, doc_start=None, dropout_p: float = 0.0):
+    """Shapes outside the kernels' range (and every packed-document or dropout call off the GPU): explicit masked
     softmax(Q K^T) V in fp32 torch ops (autograd differentiates it), result in qkv's dtype like the kernel's.
-    ``doc_start`` [B, T]: keys before the query's document are masked too."""
+    ``doc_start`` [B, T]: keys before the query's document are masked too.  ``dropout_p``: F.dropout on P (torch's
+    generator and the true p, not the kernels' Philox mask and 8-bit rate: the same distribution up to that)."""
     q, k, v = qkv5.float().permute(2, 0, 3, 1, 4)  # each [B, H, T, D]
     T = q.shape[-2]
     s = (q @ k.transpose(-1, -2)) * scale
@@ -759,16 +895,34 @@ def _causal_attention_torch(qkv5, scale: float, doc_start=None):
     if doc_start is not None:
         j = torch.arange(T, device=s.device)
         s = s.masked_fill((j[None, None, :] < doc_start.long()[:, :, None]).unsqueeze(1), float("-inf"))
-    o = torch.softmax(s, dim=-1) @ v
+    pr = torch.softmax(s, dim=-1)
+    if dropout_p > 0.0:
+        pr = F.dropout(pr, dropout_p, True)
+    o = pr @ v
     return o.transpose(1, 2).to(qkv5.dtype)  # [B, T, H, D]
 
 
-def causal_attention(qkv, n_head: int, doc_bounds=None):
+def causal_attention(qkv, n_head: int, doc_bounds=None, dropout_p: float = 0.0, rng=None, stream: int = 0):
     """qkv: [B, T, 3*H*D] -> [B, T, H*D] causal softmax attention.  ``doc_bounds`` (the tuple doc_bounds()
-    returns): attention stays inside each packed document."""
+    returns): attention stays inside each packed document.  ``dropout_p`` > 0 (training; the caller decides):
+    dropout on the attention probabilities -- inside the flash kernels at the rate attn_dropout_rate(dropout_p),
+    with the mask drawn from ``rng`` (a DropoutState snapshot, default: a fresh one, after which the state is
+    advanced) and ``stream``; off the GPU or for other shapes an explicit softmax with F.dropout on P."""
     B, T, three_hd = qkv.shape
     D = three_hd // (3 * n_head)
     scale = 1.0 / math.sqrt(D)
+    if dropout_p != 0.0:
+        if not 0.0 < dropout_p < 1.0:
+            raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
+        ds, de = (doc_bounds[0], doc_bounds[1]) if doc_bounds is not None else (None, None)
+        if not qkv.is_cuda or not attn_kernel_ok(T, D):
+            return _causal_attention_torch(qkv.reshape(B, T, 3, n_head, D), scale, ds, dropout_p).reshape(B, T, n_head * D)
+        if rng is None:
+            st = dropout_state(qkv.device)
+            rng = st.snapshot()
+            st.advance(B * n_head * (T // 4) ** 2)
+        out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, ds, de, dropout_p, rng, stream)
+        return out.reshape(B, T, n_head * D)
     if doc_bounds is not None:
         ds, de = doc_bounds[0], doc_bounds[1]
         if not qkv.is_cuda or not attn_kernel_ok(T, D):

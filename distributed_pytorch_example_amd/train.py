@@ -70,6 +70,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "validation loss stays the plain cross-entropy, the logged train loss includes the regularisers")
     p.add_argument("--z-loss", type=float, default=0.0,
                    help="weight of the z-loss (mean logsumexp^2) added to the training loss; validation stays plain")
+    p.add_argument("--dropout", type=float, default=0.0,
+                   help="gpt2 models: dropout rate in [0, 1) on the embedding sum, the attention probabilities (inside "
+                        "the flash kernels, at the 8-bit rate round(256 p) / 256) and both residual branches; training "
+                        "only (validation runs in eval mode); the mask state lives on the device and is not checkpointed")
     p.add_argument("--bucket-mb", type=float, default=None,
                    help="gradient bucket cap (default: the 7-link xGMI policy, parallel/buckets.py)")
     p.add_argument("--last-bucket-mb", type=float, default=None,
@@ -242,6 +246,10 @@ def main(argv=None):
         parser.error("--label-smoothing must be in [0, 1)")
     if not args.z_loss >= 0.0:
         parser.error("--z-loss must be >= 0")
+    if not 0.0 <= args.dropout < 1.0:
+        parser.error("--dropout must be in [0, 1)")
+    if args.dropout > 0.0 and not args.model.startswith("gpt2"):
+        parser.error("--dropout needs a gpt2 model")
     ensure_single_process_env()
     rank, world_size, local_rank = pdist.init_process_group(args.backend, comm_max_channels=args.comm_max_channels)
     logger.info(f"Initialized process group: rank={rank}, world_size={world_size}, local_rank={local_rank}")
@@ -250,7 +258,7 @@ def main(argv=None):
     logger.info(f"Starting distributed training with {world_size} processes")
     logger.info(f"Configuration: epochs={args.epochs}, batch_size={args.batch_size}, lr={args.lr}")
 
-    reg_kw = {"label_smoothing": args.label_smoothing, "z_loss": args.z_loss}
+    reg_kw = {"label_smoothing": args.label_smoothing, "z_loss": args.z_loss, "dropout": args.dropout}
     model = get_model(args.model, **_dtype_kw(args), **(reg_kw if args.model.startswith("gpt2") else {})).to(device)
     model = DDP(model, bucket_cap_mb=args.bucket_mb,
                 last_bucket_mb="auto" if args.last_bucket_mb is None else (args.last_bucket_mb or None),
