@@ -64,6 +64,7 @@ class Block(nn.Module):
         # and per-op paths alike): DDP may leave them out of the gradient re-zero (ops/_state.py)
         for lin in (self.c_attn, self.attn_proj, self.c_fc, self.mlp_proj):
             lin.weight._dpe_overwrite_ok = True
+        self.c_attn.weight._dpe_muon_split = 3  # optim.Muon orthogonalises the Q, K and V row blocks separately
 
     def forward(self, x, doc=None, drop=None):
         """``doc``: the (doc_start, doc_end, pos) of Fx.doc_bounds for packed documents, None for one per row.
@@ -108,6 +109,7 @@ class GPT2(nn.Module):
         # tied LM head / embedding: the LM-head weight grad (first writer) overwrites when fresh, the
         # embedding scatter-add accumulates after it
         self.wte._dpe_overwrite_ok = True
+        self.wte._dpe_muon = self.wpe._dpe_muon = False  # embeddings / LM head: build_optimizer("muon") keeps them on AdamW
         self._init()
 
     def _init(self):

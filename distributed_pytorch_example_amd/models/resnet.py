@@ -99,6 +99,7 @@ class ResNet(nn.Module):
                 inplanes = planes * 4
         self.blocks = nn.Sequential(*blocks)
         self.fc = Linear(512 * 4, num_classes, out_f32=True)
+        self.fc.weight._dpe_muon = False  # the output layer: build_optimizer("muon") keeps it on AdamW
 
     def forward(self, x):
         """x: NCHW float images [N,3,H,W], or packed on the GPU: space-to-depth

@@ -95,6 +95,7 @@ class SimpleNet(nn.Module):
             Dropout(0.2),
             Linear(hidden_size, num_classes, out_f32=True),
         )
+        self.layers[-1].weight._dpe_muon = False  # the output layer: build_optimizer("muon") keeps it on AdamW
 
     def forward(self, x):
         x = self.flatten(x)

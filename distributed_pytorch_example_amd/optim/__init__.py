@@ -1,8 +1,8 @@
 import torch
 
-from .fused import LAMB, LARS, SGD, Adam, AdamW, _CLIP_BUF, _pack_desc, lr_factor
+from .fused import LAMB, LARS, SGD, Adam, AdamW, Muon, _CLIP_BUF, _pack_desc, lr_factor, newton_schulz
 
-__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "build_optimizer", "clip_grad_norm_", "lr_factor"]
+__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "Muon", "build_optimizer", "clip_grad_norm_", "lr_factor", "newton_schulz"]
 
 
 def _trust_groups(params, weight_decay, off):
@@ -20,10 +20,36 @@ def _trust_groups(params, weight_decay, off):
     return groups
 
 
-def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, momentum: float = 0.9, *,
-                    clip_grad_norm=None, skip_nonfinite: bool = False, trust_coefficient=None, lr_schedule=None):
+def _muon_groups(params, weight_decay):
+    """A flat parameter list becomes three groups: Muon for the matrices (2-D, not marked ``_dpe_muon = False``,
+    every dimension of every row block a multiple of 8, the envelope of bf16 MFMA kernels), AdamW with the
+    weight decay for the other tensors with ndim > 1 (embeddings, output layers, conv filters), AdamW without it
+    for ndim <= 1.  Param groups the caller made are kept as they are."""
+    params = list(params)
+    if not params or isinstance(params[0], dict):
+        return params
+
+    def takes(p):
+        s = int(getattr(p, "_dpe_muon_split", 1) or 1)
+        return (p.ndim == 2 and getattr(p, "_dpe_muon", True) and p.shape[0] % s == 0 and (p.shape[0] // s) % 8 == 0
+                and p.shape[1] % 8 == 0)
+
+    groups = [{"params": [p for p in params if takes(p)], "use_muon": True},
+              {"params": [p for p in params if p.ndim > 1 and not takes(p)], "use_muon": False},
+              {"params": [p for p in params if p.ndim <= 1], "use_muon": False, "weight_decay": 0.0}]
+    return [g for g in groups if g["params"]]
+
+
+def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, momentum=None, *,
+                    clip_grad_norm=None, skip_nonfinite: bool = False, trust_coefficient=None, lr_schedule=None,
+                    ns_steps=None):
     """``lr_schedule``: a dict of ``set_lr_schedule``'s arguments (``kind``, ``total_steps`` and optionally
-    ``warmup_steps``, ``min_ratio``, ``power``)."""
+    ``warmup_steps``, ``min_ratio``, ``power``).  ``momentum`` defaults to 0.9, for ``"muon"`` to 0.95;
+    ``ns_steps`` is Muon's."""
+    if ns_steps is not None and name.lower() != "muon":
+        raise ValueError(f"ns_steps is for muon, not {name!r}")
+    if momentum is None:
+        momentum = 0.95 if name.lower() == "muon" else 0.9
     name = name.lower()
     if lr_schedule is not None:
         lr_schedule = dict(lr_schedule)
@@ -48,6 +74,9 @@ def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, mom
             raise ValueError(f"Invalid trust_coefficient: {trust_coefficient}")
         opt = LAMB(_trust_groups(params, weight_decay, {"trust_ratio": False}), lr=lr, weight_decay=weight_decay,
                    trust_ratio=trust_coefficient is None or trust_coefficient > 0)
+    elif name == "muon":
+        opt = Muon(_muon_groups(params, weight_decay), lr=lr, momentum=momentum, weight_decay=weight_decay,
+                   ns_steps=5 if ns_steps is None else ns_steps, scale="match_rms")
     else:
         raise ValueError(f"unknown optimizer {name!r}")
     if clip_grad_norm is not None or skip_nonfinite:

@@ -25,6 +25,9 @@ written back, the host is not involved, and the step still replays in a graph.
 A learning-rate schedule (``set_lr_schedule``: warm-up, then constant / linear / cosine / polynomial decay)
 is evaluated on the device too: a one-block kernel turns a device step counter into this step's lr inside the
 hyper-parameter block, so no host copy happens per step and a captured step replays with an advancing lr.
+
+``Muon`` (at the end of this file) shares the clip / schedule / state-dict machinery but has no GPU kernels yet:
+it runs its formulas in torch ops on CPU parameters and raises on GPU parameters.
 """
 from __future__ import annotations
 
@@ -780,3 +783,156 @@ class LAMB(Adam):
                 rows.append([float(wn), float(un), float(ratio)])
                 p.add_(u * ratio, alpha=-lr)
         self._cpu_stats(rows)
+
+
+# ------------------------------------------------------------------ Muon
+NS_COEFFICIENTS = (3.4445, -4.7750, 2.0315)
+_MUON_SCALES = ("match_rms", "spectral")
+
+
+def muon_gamma(scale: str, rows: int, cols: int) -> float:
+    """The update's scale for one orthogonalised ``[rows, cols]`` block."""
+    if scale == "match_rms":
+        return 0.2 * math.sqrt(max(rows, cols))
+    if scale == "spectral":
+        return math.sqrt(max(1.0, rows / cols))
+    raise ValueError(f"Muon: scale must be one of {_MUON_SCALES}, got {scale!r}")
+
+
+def newton_schulz(u, ns_steps: int = 5, coefficients=NS_COEFFICIENTS):
+    """``NS_k(u)`` of one fp32 ``[rows, cols]`` block in torch ops: ``X = u / (|u|_F + 1e-7)`` rounded to bf16,
+    then ``ns_steps`` times ``A = X X^T, B = b A + c A A, X = a X + B X`` (a tall block takes the Gram matrix of
+    its short side: ``A = X^T X, X = a X + X B``; no transposed copy).  ``X``, ``A`` and ``B`` are bf16 tensors
+    between the products; every product takes bf16 operands and accumulates in fp32, and its epilogue
+    (``b A + c acc``, ``a X + acc``) is rounded to bf16 once.  Returns bf16."""
+    a, b, c = (float(v) for v in coefficients)
+    X = (u.float() / (u.float().norm() + 1e-7)).bfloat16()
+    tall = X.shape[0] > X.shape[1]
+    for _ in range(int(ns_steps)):
+        Xf = X.float()
+        A = (Xf.T @ Xf if tall else Xf @ Xf.T).bfloat16()
+        Af = A.float()
+        B = (b * Af + c * (Af @ Af)).bfloat16()
+        X = (a * Xf + (Xf @ B.float() if tall else B.float() @ Xf)).bfloat16()
+    return X
+
+
+def _muon_split(p) -> int:
+    return int(getattr(p, "_dpe_muon_split", 1) or 1)
+
+
+class Muon(_FusedMixin, torch.optim.Optimizer):
+    """Muon (momentum SGD with a Newton-Schulz-orthogonalised update) for the hidden weight matrices and the
+    AdamW rule for everything else, in one optimizer.  The per-group key ``use_muon`` selects the rule.  For a
+    ``[rows, cols]`` parameter of a Muon group, with ``g'`` the gradient after clipping and ``maximize``:
+
+        buf = buf + (1 - momentum) (g' - buf)
+        u   = g' + momentum (buf - g')   if nesterov else   buf
+        O   = NS_k(u)                    per block when ``p._dpe_muon_split = s`` splits the rows in s blocks
+        W   = W (1 - lr weight_decay) - lr gamma O
+
+    ``NS_k``: ``newton_schulz`` above.  ``gamma`` is ``0.2 sqrt(max(rows, cols))`` of the block for
+    ``scale="match_rms"`` (the update's RMS is about AdamW's, so one lr and one weight decay serve both kinds of
+    group) and ``sqrt(max(1, rows / cols))`` for ``"spectral"``.  Muon groups keep SGD's state schema
+    (``momentum_buffer``); the other groups take torch.optim.AdamW's own update and state keys, so on them the
+    result is ``optim.AdamW``'s bit for bit.  ``set_grad_clip`` (one global norm over all groups),
+    ``set_lr_schedule``, ``grad_norm``, ``current_lr`` and the state dict work as for the other optimizers.
+
+    The formulas run in torch ops on CPU parameters.  There are no GPU kernels for it yet: a step on GPU
+    parameters raises instead of falling back to eager torch (docs/perf_notes.md, "Muon")."""
+
+    _kind = 0
+    _whole_matrix = True  # DDP.overlap_optimizer refuses it: whole matrices, after the whole backward
+
+    def __init__(self, params, lr=1e-3, momentum=0.95, nesterov=True, ns_steps=5, ns_coefficients=NS_COEFFICIENTS,
+                 scale="match_rms", weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, use_muon=True, *, maximize=False):
+        defaults = dict(lr=lr, use_muon=bool(use_muon), momentum=momentum, nesterov=bool(nesterov), ns_steps=ns_steps,
+                        ns_coefficients=tuple(ns_coefficients), scale=scale, weight_decay=weight_decay, betas=tuple(betas),
+                        eps=eps, maximize=bool(maximize))
+        super().__init__(params, defaults)
+        for g in self.param_groups:
+            self._check_group(g)
+        self._fused_init()
+
+    @staticmethod
+    def _check_group(g):
+        if not _lr(g) >= 0.0:
+            raise ValueError(f"Invalid learning rate: {g['lr']}")
+        if not g["weight_decay"] >= 0.0:
+            raise ValueError(f"Invalid weight_decay value: {g['weight_decay']}")
+        if g["use_muon"]:
+            if not 0.0 <= g["momentum"] < 1.0:
+                raise ValueError(f"Muon: momentum must be in [0, 1), got {g['momentum']}")
+            if int(g["ns_steps"]) != g["ns_steps"] or g["ns_steps"] < 1:
+                raise ValueError(f"Muon: ns_steps must be a positive integer, got {g['ns_steps']}")
+            if len(tuple(g["ns_coefficients"])) != 3:
+                raise ValueError("Muon: ns_coefficients is (a, b, c)")
+            if g["scale"] not in _MUON_SCALES:
+                raise ValueError(f"Muon: scale must be one of {_MUON_SCALES}, got {g['scale']!r}")
+            for p in g["params"]:
+                if p.ndim != 2:
+                    raise ValueError(f"Muon: a use_muon group takes 2-D parameters, got shape {tuple(p.shape)}")
+                if p.shape[0] % _muon_split(p) != 0:
+                    raise ValueError(f"Muon: _dpe_muon_split = {_muon_split(p)} does not divide {p.shape[0]} rows")
+        else:
+            b1, b2 = g["betas"]
+            if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and g["eps"] >= 0.0):
+                raise ValueError("Muon: invalid betas / eps in an AdamW group")
+
+    def _ov_attach(self, stream):
+        raise RuntimeError("overlap_optimizer: Muon orthogonalises whole matrices after the whole backward; it cannot "
+                           "step per bucket")
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if any(p.is_cuda for p in self._all_params()):
+            raise NotImplementedError("optim.Muon has no GPU kernels yet (batched Newton-Schulz GEMMs); it steps CPU "
+                                      "parameters only and does not fall back to eager torch ops on the GPU")
+        if not self._cpu_clip():
+            return None
+        base = self._cpu_sched_begin()
+        try:
+            self._cpu_update()
+        finally:
+            self._cpu_sched_end(base)
+        return loss
+
+    def _cpu_update(self):
+        from torch.optim.adam import adam
+
+        for group in self.param_groups:
+            lr, wd, mx = _lr(group), group["weight_decay"], group.get("maximize", False)
+            ps = [p for p in group["params"] if p.grad is not None]
+            for p in ps:
+                st = self.state[p]
+                if "step" not in st:
+                    st["step"] = torch.zeros((), dtype=torch.float32)
+                    for k in (("momentum_buffer",) if group["use_muon"] else ("exp_avg", "exp_avg_sq")):
+                        st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if not group["use_muon"]:
+                b1, b2 = group["betas"]
+                if ps:  # torch.optim.AdamW's own call, so the result is optim.AdamW's bit for bit
+                    adam(ps, [p.grad for p in ps], [self.state[p]["exp_avg"] for p in ps],
+                         [self.state[p]["exp_avg_sq"] for p in ps], [], [self.state[p]["step"] for p in ps], amsgrad=False,
+                         beta1=b1, beta2=b2, lr=lr, weight_decay=wd, eps=group["eps"], maximize=mx,
+                         decoupled_weight_decay=True)
+                continue
+            mom = group["momentum"]
+            for p in ps:
+                st = self.state[p]
+                st["step"] += 1.0
+                g = -p.grad if mx else p.grad
+                buf = st["momentum_buffer"]
+                buf.add_((g - buf) * (1.0 - mom))
+                u = g + mom * (buf - g) if group["nesterov"] else buf
+                s = _muon_split(p)
+                rows = p.shape[0] // s
+                gamma = muon_gamma(group["scale"], rows, p.shape[1])
+                p.mul_(1.0 - lr * wd)
+                for b in range(s):
+                    O = newton_schulz(u[b * rows:(b + 1) * rows], group["ns_steps"], group["ns_coefficients"])
+                    p[b * rows:(b + 1) * rows].add_(O.float(), alpha=-lr * gamma)

@@ -479,6 +479,9 @@ class DistributedDataParallel(nn.Module):
         if getattr(optimizer, "_trust", None) is not None:
             raise RuntimeError("overlap_optimizer: the optimizer scales every tensor by a layer-wise trust ratio "
                                "(LARS / LAMB), whose norms exist only after the whole backward")
+        if getattr(optimizer, "_whole_matrix", False):
+            raise RuntimeError("overlap_optimizer: Muon orthogonalises whole matrices after the whole backward; it "
+                               "cannot step per bucket")
         if not (self._params and self._params[0].is_cuda):
             raise RuntimeError("overlap_optimizer: GPU parameters only")
         if self.world_size > 1 and not self._native:

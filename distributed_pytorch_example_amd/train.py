@@ -50,7 +50,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dtype", default=None, choices=[None, "fp32", "bf16"],
                    help="compute dtype on the GPU (default: fp32 for simplenet as the reference, bf16 otherwise; "
                         "fp32 masters and gradients always)")
-    p.add_argument("--optimizer", default=None, choices=[None, "adam", "adamw", "sgd", "lars", "lamb"])
+    p.add_argument("--optimizer", default=None, choices=[None, "adam", "adamw", "sgd", "lars", "lamb", "muon"])
+    p.add_argument("--muon-momentum", type=float, default=None, help="--optimizer muon: the momentum (default 0.95)")
+    p.add_argument("--muon-ns-steps", type=int, default=None,
+                   help="--optimizer muon: Newton-Schulz iterations per step (default 5)")
     p.add_argument("--trust-coefficient", type=float, default=None,
                    help="--optimizer lars: the trust coefficient (default 1e-3); lamb: 0 turns the trust ratio off")
     p.add_argument("--weight-decay", type=float, default=0.0)
@@ -232,6 +235,13 @@ def main(argv=None):
         parser.error("--doc-len-mean must be >= 1")
     if args.trust_coefficient is not None and args.optimizer not in ("lars", "lamb"):
         parser.error("--trust-coefficient needs --optimizer lars or lamb")
+    for flag, v in (("--muon-momentum", args.muon_momentum), ("--muon-ns-steps", args.muon_ns_steps)):
+        if v is not None and args.optimizer != "muon":
+            parser.error(f"{flag} needs --optimizer muon")
+    if args.muon_momentum is not None and not 0.0 <= args.muon_momentum < 1.0:
+        parser.error("--muon-momentum must be in [0, 1)")
+    if args.muon_ns_steps is not None and args.muon_ns_steps < 1:
+        parser.error("--muon-ns-steps must be >= 1")
     if args.lr_schedule is None:
         for flag, v in (("--warmup-steps", args.warmup_steps), ("--lr-min-ratio", args.lr_min_ratio), ("--lr-power", args.lr_power)):
             if v is not None:
@@ -281,7 +291,10 @@ def main(argv=None):
     optimizer = build_optimizer(opt_name, model.parameters(), lr=args.lr, weight_decay=args.weight_decay,
                                 clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps,
                                 lr_schedule=_lr_schedule_kw(parser, args, len(train_loader)),
-                                **({"trust_coefficient": args.trust_coefficient} if opt_name in ("lars", "lamb") else {}))
+                                **({"trust_coefficient": args.trust_coefficient} if opt_name in ("lars", "lamb") else {}),
+                                **({"momentum": 0.95 if args.muon_momentum is None else args.muon_momentum,
+                                    "ns_steps": 5 if args.muon_ns_steps is None else args.muon_ns_steps}
+                                   if opt_name == "muon" else {}))
 
     def criterion(out, tgt):  # training only: validate() takes Fx.cross_entropy_eval, the plain cross-entropy
         return Fx.cross_entropy(out, tgt, num_classes, label_smoothing=args.label_smoothing, z_loss=args.z_loss)
