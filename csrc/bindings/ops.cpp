@@ -356,6 +356,62 @@ void optim_trust_step(int64_t kind, const Tensor& desc, const Tensor& chunks, co
            "optim_trust_step");
 }
 
+// The weight EMA.  `ema`: int64 [n_tensors] on the device, the fp32 average of every tensor of the table (raw
+// pointers, in table order); `blk`: fp64 [3] n, decay, warm-up; `cur`: fp32 [1], the d_n of the last step.
+static int64_t check_ema_ptrs(const char* what, const Tensor& desc, const Tensor& ema) {
+  CHECK_GPU(ema); CHECK_CONTIG(ema);
+  const int64_t db = dpe_optim_desc_bytes();
+  TORCH_CHECK(desc.scalar_type() == at::kByte && desc.numel() % db == 0, what, ": desc is a byte tensor of whole TensorDescs");
+  TORCH_CHECK(ema.scalar_type() == at::kLong && ema.numel() == desc.numel() / db, what, ": ema is int64 [n_tensors]");
+  return desc.numel() / db;
+}
+
+void optim_step_ema(int64_t kind, const Tensor& desc, const Tensor& chunks, const Tensor& hp, const Tensor& steps,
+                    const Tensor& ema) {
+  TORCH_CHECK(kind == 0 || kind == 1, "optim_step_ema: kind 0 (Adam) or 1 (SGD)");
+  check_optim_table(desc, chunks);
+  CHECK_GPU(hp); CHECK_F32(hp); CHECK_CONTIG(hp); CHECK_GPU(steps); CHECK_F32(steps); CHECK_CONTIG(steps);
+  TORCH_CHECK(hp.numel() >= 12 && hp.numel() % 12 == 0, "optim_step_ema: hp holds 12 floats per group");
+  const int64_t nt = check_ema_ptrs("optim_step_ema", desc, ema);
+  TORCH_CHECK(steps.numel() >= nt, "optim_step_ema: one step counter per tensor");
+  CHECK_RC(dpe_optim_step_ema((int)kind, desc.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), fp(hp), fp(steps),
+                              ema.data_ptr(), cur_stream()),
+           "optim_step_ema");
+}
+
+void optim_trust_step_ema(int64_t kind, const Tensor& desc, const Tensor& chunks, const Tensor& hp, const Tensor& steps,
+                          const Tensor& stats, const Tensor& ema) {
+  TORCH_CHECK(kind == 0 || kind == 1, "optim_trust_step_ema: kind 0 (LARS) or 1 (LAMB)");
+  check_optim_table(desc, chunks);
+  CHECK_GPU(stats); CHECK_F32(stats); CHECK_CONTIG(stats);
+  const int64_t nt = check_trust_args("optim_trust_step_ema", desc, hp, &steps, stats, stats, 0);
+  TORCH_CHECK(stats.numel() >= 3 * nt, "optim_trust_step_ema: stats holds 3 floats per tensor");
+  check_ema_ptrs("optim_trust_step_ema", desc, ema);
+  CHECK_RC(dpe_optim_trust_step_ema((int)kind, desc.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), fp(hp), fp(steps),
+                                    fp(stats), ema.data_ptr(), cur_stream()),
+           "optim_trust_step_ema");
+}
+
+// 1 - d_n into slot 11 of every hp row and d_n into cur[0]; the device counter blk[0] advances by the step's ok flag.
+void optim_ema_decay(Tensor& hp, Tensor& blk, Tensor& cur) {
+  CHECK_GPU(hp); CHECK_F32(hp); CHECK_CONTIG(hp);
+  CHECK_GPU(blk); CHECK_CONTIG(blk);
+  CHECK_GPU(cur); CHECK_F32(cur); CHECK_CONTIG(cur);
+  TORCH_CHECK(blk.scalar_type() == at::kDouble && blk.numel() == 3, "optim_ema_decay: blk is fp64 [3]");
+  TORCH_CHECK(hp.numel() > 0 && hp.numel() % 12 == 0, "optim_ema_decay: hp holds 12 floats per group");
+  TORCH_CHECK(cur.numel() >= 1, "optim_ema_decay: cur holds one float");
+  CHECK_RC(dpe_optim_ema_decay(fp(hp), (int)(hp.numel() / 12), (double*)blk.data_ptr(), fp(cur), cur_stream()),
+           "optim_ema_decay");
+}
+
+// w <-> ema over the table, and the bf16 shadows of the new w.
+void optim_ema_swap(const Tensor& desc, const Tensor& chunks, const Tensor& ema) {
+  check_optim_table(desc, chunks);
+  check_ema_ptrs("optim_ema_swap", desc, ema);
+  CHECK_RC(dpe_optim_ema_swap(desc.data_ptr(), chunks.data_ptr(), (int)chunks.size(0), ema.data_ptr(), cur_stream()),
+           "optim_ema_swap");
+}
+
 // -------------------------------------------------------------- LayerNorm
 // x [rows, D] (f32 or bf16) -> y bf16, mean/rstd f32 [rows]
 std::vector<Tensor> layernorm_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, double eps) {
@@ -545,6 +601,10 @@ void register_ops(pybind11::module& m) {
   m.def("optim_trust_partials", &optim_trust_partials);
   m.def("optim_trust_ratio", &optim_trust_ratio);
   m.def("optim_trust_step", &optim_trust_step);
+  m.def("optim_step_ema", &optim_step_ema);
+  m.def("optim_trust_step_ema", &optim_trust_step_ema);
+  m.def("optim_ema_decay", &optim_ema_decay, py::arg("hp"), py::arg("blk"), py::arg("cur"));
+  m.def("optim_ema_swap", &optim_ema_swap, py::arg("desc"), py::arg("chunks"), py::arg("ema"));
   m.def("optim_chunk_size", []() { return dpe_optim_chunk_size(); });
   m.def("optim_desc_bytes", []() { return dpe_optim_desc_bytes(); });
   m.def("layernorm_bwd_residual", &layernorm_bwd_residual, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"),

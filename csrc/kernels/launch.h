@@ -132,6 +132,13 @@ int dpe_optim_trust_ratio(int kind, const void* desc, int ntensors, const int* f
                           const float* part_x, const float* hp, float* stats, hipStream_t st);
 int dpe_optim_trust_step(int kind, const void* desc, const void* chunks, int nchunks, const float* hp, const float* steps,
                          const float* stats, hipStream_t st);
+// the weight EMA (ema: device array of one fp32 pointer per tensor of the table; blk: fp64 [3] n, decay, warm-up)
+int dpe_optim_step_ema(int kind, const void* desc, const void* chunks, int nchunks, const float* hp, const float* steps,
+                       const void* ema, hipStream_t st);
+int dpe_optim_trust_step_ema(int kind, const void* desc, const void* chunks, int nchunks, const float* hp, const float* steps,
+                             const float* stats, const void* ema, hipStream_t st);
+int dpe_optim_ema_decay(float* hp, int ngroups, double* blk, float* cur, hipStream_t st);
+int dpe_optim_ema_swap(const void* desc, const void* chunks, int nchunks, const void* ema, hipStream_t st);
 // ---- norm.hip
 int dpe_layernorm_fwd(const void* x, int x_bf16, const float* w, const float* b, uint16_t* y, float* mean, float* rstd,
                       int64_t rows, int D, float eps, hipStream_t st);

@@ -32,6 +32,7 @@ struct TensorDesc {
 // The host initialises coef and ok to 1.0; grad_clip_coef_kernel overwrites them when clipping is on.
 constexpr int HP = 12;
 constexpr int HP_COEF = 7, HP_OK = 8;
+constexpr int HP_EMA = 11;  // 1 - d_n of the weight EMA (ema_decay_kernel; the EMA kernels alone read it)
 // 16K elements per block: 256 lanes x 4 (one 16-B access per operand) x 16
 // iterations.  Small enough that a 25M-parameter model spreads over ~1.6k
 // blocks (>6 per CU, so the streaming loads of several waves overlap), large
@@ -87,17 +88,66 @@ struct SgdRule {
   }
 };
 
+// The weight-EMA operand of a 16-B walk (optim_chunk, lamb_chunk): its own resource, the look-ahead register and
+// ema += ew * (p_new - ema), ew = 1 - d_n.  With ew == 1 (the first update, ema == 0) that is 0 + 1 * (p - 0): p
+// bit for bit.  The EMA = false arm is empty, so the kernels without the average are what they were before it.
+template <bool EMA>
+struct EmaArm {
+  DPE_DEVICE EmaArm(const float*, uint32_t, float) {}
+  DPE_DEVICE void load(uint32_t) {}
+  DPE_DEVICE void take() {}
+  DPE_DEVICE void update(int, float) {}
+  DPE_DEVICE void store(uint32_t) const {}
+};
+
+template <>
+struct EmaArm<true> {
+  __amdgpu_buffer_rsrc_t rs;
+  float ew;
+  f32x4 next, cur;
+  DPE_DEVICE EmaArm(const float* base, uint32_t bytes, float ew_) : rs(buf_rsrc(base, bytes)), ew(ew_) {}
+  DPE_DEVICE void load(uint32_t o) { next = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 0)); }
+  DPE_DEVICE void take() { cur = next; }
+  DPE_DEVICE void update(int e, float p) { cur[e] = cur[e] + ew * (p - cur[e]); }
+  DPE_DEVICE void store(uint32_t o) const { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, cur), rs, o, 0, 0); }
+};
+
+// The same for lamb_chunk's one-element-per-lane end.
+template <bool EMA>
+struct EmaTail {
+  DPE_DEVICE EmaTail(const float*, uint32_t, float) {}
+  DPE_DEVICE void load(uint32_t) {}
+  DPE_DEVICE void store(uint32_t, float) const {}
+};
+
+template <>
+struct EmaTail<true> {
+  __amdgpu_buffer_rsrc_t rs;
+  float ew, a;
+  DPE_DEVICE EmaTail(const float* base, uint32_t bytes, float ew_) : rs(buf_rsrc(base, bytes)), ew(ew_), a(0.f) {}
+  DPE_DEVICE void load(uint32_t o) { a = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0)); }
+  DPE_DEVICE void store(uint32_t o, float p) const {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a + ew * (p - a)), rs, o, 0, 0);
+  }
+};
+
 // One (tensor, chunk) per block.  When every operand of the tensor is 16-B
 // aligned (8-B for the bf16 shadow) -- always the case for parameters and for
 // bucket-view gradients of 4-multiple sizes -- each lane moves 4 elements per
 // operand per iteration with dwordx4 loads/stores; otherwise (or for the
 // ragged tail) one element.  `s2` is only touched by rules that use it.
-template <class Rule, bool TWO_STATES>
-DPE_DEVICE void optim_chunk(const TensorDesc& d, const Rule& rule, int chunk) {
+//
+// EMA: the weight average rides along, ema += ew * (p_new - ema) with ew = 1 - d_n (ew == 1 on the first
+// update: 0 + 1 * (p - 0) is p bit for bit).  One more operand of the same walk -- its load joins the
+// look-ahead loads and its store the stores, both unconditional through a resource of its own.  `ema` is
+// the tensor's fp32 average (never null when EMA); the EMA = false instantiations do not see either argument.
+template <class Rule, bool TWO_STATES, bool EMA = false>
+DPE_DEVICE void optim_chunk(const TensorDesc& d, const Rule& rule, int chunk, float* ema = nullptr, float ew = 0.f) {
   const int64_t beg = (int64_t)chunk * CHUNK;
   const int64_t end = min(d.n, beg + CHUNK);
   const bool has_s1 = d.s1 != nullptr;
-  const uintptr_t align = (uintptr_t)d.p | (uintptr_t)d.g | (uintptr_t)d.s1 | (TWO_STATES ? (uintptr_t)d.s2 : 0);
+  const uintptr_t align = (uintptr_t)d.p | (uintptr_t)d.g | (uintptr_t)d.s1 | (TWO_STATES ? (uintptr_t)d.s2 : 0) |
+                          (EMA ? (uintptr_t)ema : 0);
   const bool vec = (align & 15) == 0 && ((uintptr_t)d.shadow & 7) == 0;
   int64_t i = beg;
   if (vec) {
@@ -119,23 +169,29 @@ DPE_DEVICE void optim_chunk(const TensorDesc& d, const Rule& rule, int chunk) {
     };
     const uint32_t lo = threadIdx.x * 16u;  // the lane's 16 B of a 4-KiB step
     f32x4 pn = ld(prs, lo), gn = ld(grs, lo), mn = ld(mrs, lo), vn = ld(vrs, lo);
+    EmaArm<EMA> arm(ema + beg, bytes, ew);
+    arm.load(lo);
     for (int k = 0; k < nsteps; ++k) {
       f32x4 p = pn, m = mn, v = vn;
       const f32x4 g = gn;
+      arm.take();
       const uint32_t o = lo + (uint32_t)k * 4096u, on = k + 1 < nsteps ? o + 4096u : o;
       pn = ld(prs, on);
       gn = ld(grs, on);
       mn = ld(mrs, on);
       vn = ld(vrs, on);
+      arm.load(on);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = p[e], me = m[e], ve = v[e];
         rule(pe, g[e], me, ve);
         p[e] = pe; m[e] = me; v[e] = ve;
+        arm.update(e, pe);
       }
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, p), prs, o, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), mrs, o, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), vrs, o, 0, 0);
+      arm.store(o);
       u32x2 sh;
       sh[0] = pack_bf2(p[0], p[1]);
       sh[1] = pack_bf2(p[2], p[3]);
@@ -150,6 +206,10 @@ DPE_DEVICE void optim_chunk(const TensorDesc& d, const Rule& rule, int chunk) {
     if (has_s1) d.s1[j] = m;
     if (TWO_STATES) d.s2[j] = v;
     if (d.shadow) d.shadow[j] = f2bf(p);
+    if (EMA) {
+      const float a = ema[j];
+      ema[j] = a + ew * (p - a);
+    }
   }
 }
 
@@ -169,6 +229,28 @@ __global__ __launch_bounds__(256) void sgd_kernel(const TensorDesc* __restrict__
   const float* h = hp + d.group * HP;
   if (h[HP_OK] == 0.f) return;  // skipped step (non-finite gradient norm): uniform over the grid
   optim_chunk<SgdRule, false>(d, SgdRule(h, steps[d.step_idx]), ck.y);
+}
+
+// The same updates with the weight EMA arm.  `ema[ti]` is tensor ti's average: a device array of its own, so
+// TensorDesc and the kernels above are what they were without it.
+__global__ __launch_bounds__(256) void adam_ema_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                       const float* __restrict__ hp, const float* __restrict__ steps,
+                                                       float* const* __restrict__ ema) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const float* h = hp + d.group * HP;
+  if (h[HP_OK] == 0.f) return;  // skipped step: the average stays too
+  optim_chunk<AdamRule, true, true>(d, AdamRule(h, steps[d.step_idx]), ck.y, ema[ck.x], h[HP_EMA]);
+}
+
+__global__ __launch_bounds__(256) void sgd_ema_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                      const float* __restrict__ hp, const float* __restrict__ steps,
+                                                      float* const* __restrict__ ema) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const float* h = hp + d.group * HP;
+  if (h[HP_OK] == 0.f) return;
+  optim_chunk<SgdRule, false, true>(d, SgdRule(h, steps[d.step_idx]), ck.y, ema[ck.x], h[HP_EMA]);
 }
 
 // ------------------------------------------------------- global-norm gradient clipping
@@ -413,6 +495,16 @@ __global__ __launch_bounds__(256) void lars_kernel(const TensorDesc* __restrict_
   optim_chunk<LarsRule, false>(d, LarsRule(h, steps[d.step_idx], stats[ck.x * 3 + 2]), ck.y);
 }
 
+__global__ __launch_bounds__(256) void lars_ema_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                       const float* __restrict__ hp, const float* __restrict__ steps,
+                                                       const float* __restrict__ stats, float* const* __restrict__ ema) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const float* h = hp + d.group * HP;
+  if (h[HP_OK] == 0.f) return;
+  optim_chunk<LarsRule, false, true>(d, LarsRule(h, steps[d.step_idx], stats[ck.x * 3 + 2]), ck.y, ema[ck.x], h[HP_EMA]);
+}
+
 struct LambRule {
   float lr, b1, b2, eps, wd, gscale, rbc1, rbc2;
   bool maximize;
@@ -446,12 +538,16 @@ struct LambRule {
 // One (tensor, chunk) of LAMB.  PHASE 1: m, v <- g; sw += p^2, su += u^2 (the lane's share).  PHASE 2:
 // p -= lr_ratio * u, bf16 shadow.  The walk is optim_chunk's: 16-B steps pipelined one ahead through buffer
 // resources; the ragged end (or a whole chunk of a tensor that is not 16-B aligned) goes one element per
-// lane through resources clamped to the chunk, so no load or store is predicated there either.
-template <int PHASE>
-DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk, float lr_ratio, float& sw, float& su) {
+// lane through resources clamped to the chunk, so no load or store is predicated there either.  EMA (phase 2
+// only): the weight average as in optim_chunk, one more operand of both walks.
+template <int PHASE, bool EMA = false>
+DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk, float lr_ratio, float& sw, float& su,
+                           float* ema = nullptr, float ew = 0.f) {
+  static_assert(!EMA || PHASE == 2, "the average follows the weights phase 2 writes");
   const int64_t beg = (int64_t)chunk * CHUNK;
   const int64_t end = min(d.n, beg + CHUNK);
-  const uintptr_t align = (uintptr_t)d.p | (uintptr_t)d.s1 | (uintptr_t)d.s2 | (PHASE == 1 ? (uintptr_t)d.g : 0);
+  const uintptr_t align = (uintptr_t)d.p | (uintptr_t)d.s1 | (uintptr_t)d.s2 | (PHASE == 1 ? (uintptr_t)d.g : 0) |
+                          (EMA ? (uintptr_t)ema : 0);
   const bool vec = (align & 15) == 0 && (PHASE == 1 || ((uintptr_t)d.shadow & 7) == 0);
   const bool has_sh = PHASE == 2 && d.shadow != nullptr;
   f32x4 aw = {0.f, 0.f, 0.f, 0.f}, au = aw;
@@ -470,14 +566,18 @@ DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk,
     const uint32_t lo = threadIdx.x * 16u;
     f32x4 pn = ld(prs, lo), mn = ld(mrs, lo), vn = ld(vrs, lo), gn = pn;
     if (PHASE == 1) gn = ld(grs, lo);
+    EmaArm<EMA> arm(ema + beg, bytes, ew);
+    arm.load(lo);
     for (int k = 0; k < nsteps; ++k) {
       f32x4 p = pn, m = mn, v = vn;
       const f32x4 g = gn;
+      arm.take();
       const uint32_t o = lo + (uint32_t)k * 4096u, on = k + 1 < nsteps ? o + 4096u : o;
       pn = ld(prs, on);
       if (PHASE == 1) gn = ld(grs, on);
       mn = ld(mrs, on);
       vn = ld(vrs, on);
+      arm.load(on);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float me = m[e], ve = v[e];
@@ -489,6 +589,7 @@ DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk,
           au[e] += u * u;
         } else {
           p[e] -= lr_ratio * u;
+          arm.update(e, p[e]);
         }
       }
       if (PHASE == 1) {
@@ -500,6 +601,7 @@ DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk,
         sh[0] = pack_bf2(p[0], p[1]);
         sh[1] = pack_bf2(p[2], p[3]);
         __builtin_amdgcn_raw_buffer_store_b64(sh, srs, o >> 1, 0, 0);
+        arm.store(o);
       }
     }
     i = vend;
@@ -509,6 +611,7 @@ DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk,
   const __amdgpu_buffer_rsrc_t prs = buf_rsrc(d.p + i, tb), mrs = buf_rsrc(d.s1 + i, tb), vrs = buf_rsrc(d.s2 + i, tb);
   const __amdgpu_buffer_rsrc_t grs = buf_rsrc(PHASE == 1 ? d.g + i : nullptr, PHASE == 1 ? tb : 0u);
   const __amdgpu_buffer_rsrc_t srs = buf_rsrc(has_sh ? d.shadow + i : nullptr, has_sh ? tb / 2 : 0u);
+  EmaTail<EMA> tail(ema + i, tb, ew);
   auto ld1 = [](__amdgpu_buffer_rsrc_t r, uint32_t o) {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, o, 0, 0));
   };
@@ -516,6 +619,7 @@ DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk,
   for (int k = 0; k < nt; ++k) {
     const uint32_t o = ((uint32_t)k * 256u + threadIdx.x) * 4u;  // past tb: reads 0, the stores are dropped
     float p = ld1(prs, o), m = ld1(mrs, o), v = ld1(vrs, o);
+    tail.load(o);
     if (PHASE == 1) {
       rule.moments(ld1(grs, o), m, v);
       const float u = rule.update(p, m, v);
@@ -527,6 +631,7 @@ DPE_DEVICE void lamb_chunk(const TensorDesc& d, const LambRule& rule, int chunk,
       p -= lr_ratio * rule.update(p, m, v);
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(p), prs, o, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b16(f2bf(p), srs, o >> 1, 0, 0);
+      tail.store(o, p);
     }
   }
   sw = ((aw[0] + aw[1]) + (aw[2] + aw[3])) + tw;
@@ -554,6 +659,17 @@ __global__ __launch_bounds__(256) void lamb_phase2_kernel(const TensorDesc* __re
   if (h[HP_OK] == 0.f) return;
   float sw, su;
   lamb_chunk<2>(d, LambRule(h, steps[d.step_idx]), ck.y, h[0] * stats[ck.x * 3 + 2], sw, su);
+}
+
+__global__ __launch_bounds__(256) void lamb_phase2_ema_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                              const float* __restrict__ hp, const float* __restrict__ steps,
+                                                              const float* __restrict__ stats, float* const* __restrict__ ema) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  const float* h = hp + d.group * HP;
+  if (h[HP_OK] == 0.f) return;
+  float sw, su;
+  lamb_chunk<2, true>(d, LambRule(h, steps[d.step_idx]), ck.y, h[0] * stats[ck.x * 3 + 2], sw, su, ema[ck.x], h[HP_EMA]);
 }
 
 // One wave per tensor: lane l sums partials first + l, first + l + 64, ... in fp64, then a butterfly.  Of
@@ -595,6 +711,60 @@ __global__ __launch_bounds__(64) void trust_ratio_kernel(const TensorDesc* __res
   }
 }
 
+// ------------------------------------------------------- weight EMA: this step's decay, and the swap
+// EMA block `blk` (fp64): [0] n, the updates already done   [1] decay   [2] warm-up on / off.
+//   d_0 = 0 (the first update copies),  d_n = warm-up ? min(decay, (1 + n) / (10 + n)) : decay
+// 1 - d_n, evaluated in fp64 and rounded once, goes into every group's hp row (HP_EMA) and d_n into cur[0]; the
+// counter then advances by the step's ok flag (final by now, as for lr_schedule_kernel), so a skipped step
+// makes no update and consumes no warm-up step.
+__global__ __launch_bounds__(64) void ema_decay_kernel(float* __restrict__ hp, int ngroups, double* __restrict__ blk,
+                                                       float* __restrict__ cur) {
+  const double n = blk[0], decay = blk[1];
+  const float ok = hp[HP_OK];  // the same in every row
+  double dn = 0.0;
+  if (n >= 1.0) dn = blk[2] != 0.0 ? fmin(decay, (1.0 + n) / (10.0 + n)) : decay;
+  const float ew = (float)(1.0 - dn);
+  for (int g = threadIdx.x; g < ngroups; g += 64) hp[g * HP + HP_EMA] = ew;
+  __syncthreads();  // every thread has read n
+  if (threadIdx.x == 0) {
+    cur[0] = (float)dn;
+    blk[0] = n + (double)ok;
+  }
+}
+
+// w <-> ema element for element over the table, and the bf16 shadow of the new w (optimizer.swap_ema()).
+// Not on the training path: plain 16-B accesses where the three pointers allow, else one element per lane.
+__global__ __launch_bounds__(256) void ema_swap_kernel(const TensorDesc* __restrict__ td, const int2* __restrict__ chunks,
+                                                       float* const* __restrict__ ema) {
+  const int2 ck = chunks[blockIdx.x];
+  const TensorDesc d = td[ck.x];
+  float* a = ema[ck.x];
+  const int64_t beg = (int64_t)ck.y * CHUNK;
+  const int64_t end = min(d.n, beg + CHUNK);
+  int64_t i = beg;
+  if ((((uintptr_t)d.p | (uintptr_t)a) & 15) == 0 && ((uintptr_t)d.shadow & 7) == 0) {  // beg is a multiple of 16 B
+    const int64_t vend = beg + ((end - beg) & ~(int64_t)3);
+    for (int64_t j = beg + (int64_t)threadIdx.x * 4; j < vend; j += 1024) {
+      const f32x4 w = *reinterpret_cast<const f32x4*>(d.p + j), e = *reinterpret_cast<const f32x4*>(a + j);
+      *reinterpret_cast<f32x4*>(d.p + j) = e;
+      *reinterpret_cast<f32x4*>(a + j) = w;
+      if (d.shadow) {
+        u32x2 sh;
+        sh[0] = pack_bf2(e[0], e[1]);
+        sh[1] = pack_bf2(e[2], e[3]);
+        *reinterpret_cast<u32x2*>(d.shadow + j) = sh;
+      }
+    }
+    i = vend;
+  }
+  for (int64_t j = i + threadIdx.x; j < end; j += 256) {
+    const float w = d.p[j], e = a[j];
+    d.p[j] = e;
+    a[j] = w;
+    if (d.shadow) d.shadow[j] = f2bf(e);
+  }
+}
+
 }  // namespace dpe
 
 using namespace dpe;
@@ -610,6 +780,34 @@ extern "C" int dpe_optim_step(int kind, const void* desc, const void* chunks, in
     hipLaunchKernelGGL(adam_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp, steps);
   else
     hipLaunchKernelGGL(sgd_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp, steps);
+  return 0;
+}
+
+// The same step with the weight EMA: ema = device array of one fp32 pointer per tensor of the table.
+extern "C" int dpe_optim_step_ema(int kind, const void* desc, const void* chunks, int nchunks, const float* hp,
+                                  const float* steps, const void* ema, hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  if (kind == 0)
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp, steps,
+                       (float* const*)ema);
+  else
+    hipLaunchKernelGGL(sgd_ema_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp, steps,
+                       (float* const*)ema);
+  return 0;
+}
+
+// 1 - d_n into hp[g * HP + 11] and d_n into cur[0], then the counter in blk[0] advances by hp[HP_OK].
+// blk holds 3 doubles (see ema_decay_kernel).
+extern "C" int dpe_optim_ema_decay(float* hp, int ngroups, double* blk, float* cur, hipStream_t st) {
+  if (ngroups <= 0) return 0;
+  hipLaunchKernelGGL(ema_decay_kernel, dim3(1), dim3(64), 0, st, hp, ngroups, blk, cur);
+  return 0;
+}
+
+extern "C" int dpe_optim_ema_swap(const void* desc, const void* chunks, int nchunks, const void* ema, hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks,
+                     (float* const*)ema);
   return 0;
 }
 
@@ -678,6 +876,18 @@ extern "C" int dpe_optim_trust_step(int kind, const void* desc, const void* chun
   else
     hipLaunchKernelGGL(lamb_phase2_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp,
                        steps, stats);
+  return 0;
+}
+
+extern "C" int dpe_optim_trust_step_ema(int kind, const void* desc, const void* chunks, int nchunks, const float* hp,
+                                        const float* steps, const float* stats, const void* ema, hipStream_t st) {
+  if (nchunks <= 0) return 0;
+  if (kind == 0)
+    hipLaunchKernelGGL(lars_ema_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp, steps,
+                       stats, (float* const*)ema);
+  else
+    hipLaunchKernelGGL(lamb_phase2_ema_kernel, dim3(nchunks), dim3(256), 0, st, (const TensorDesc*)desc, (const int2*)chunks, hp,
+                       steps, stats, (float* const*)ema);
   return 0;
 }
 

@@ -782,7 +782,8 @@ def embedding(idx, wte, wpe=None, pos=None):
         if wpe is not None:
             x = x + (wpe[:T].unsqueeze(0) if pos is None else F.embedding(pos.long(), wpe))
         return x
-    return _EmbFn.apply(idx, wte, wpe, shadow(wte), shadow(wpe) if wpe is not None else None,
+    # (a loader's x = tokens[:, :-1] is a strided view; the kernels index idx as one flat array)
+    return _EmbFn.apply(idx.contiguous(), wte, wpe, shadow(wte), shadow(wpe) if wpe is not None else None,
                         pos.to(torch.int32).contiguous() if pos is not None else None)
 
 

@@ -1,8 +1,9 @@
 import torch
 
-from .fused import LAMB, LARS, SGD, Adam, AdamW, Muon, _CLIP_BUF, _pack_desc, lr_factor, newton_schulz
+from .fused import LAMB, LARS, SGD, Adam, AdamW, Muon, _CLIP_BUF, _pack_desc, ema_decay_at, lr_factor, newton_schulz
 
-__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "Muon", "build_optimizer", "clip_grad_norm_", "lr_factor", "newton_schulz"]
+__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "Muon", "build_optimizer", "clip_grad_norm_", "ema_decay_at", "lr_factor",
+           "newton_schulz"]
 
 
 def _trust_groups(params, weight_decay, off):
@@ -42,8 +43,8 @@ def _muon_groups(params, weight_decay):
 
 def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, momentum=None, *,
                     clip_grad_norm=None, skip_nonfinite: bool = False, trust_coefficient=None, lr_schedule=None,
-                    ns_steps=None):
-    """``lr_schedule``: a dict of ``set_lr_schedule``'s arguments (``kind``, ``total_steps`` and optionally
+                    ns_steps=None, ema=None):
+    """``ema``: a dict of ``set_ema``'s arguments (``decay`` and optionally ``warmup``).  ``lr_schedule``: a dict of ``set_lr_schedule``'s arguments (``kind``, ``total_steps`` and optionally
     ``warmup_steps``, ``min_ratio``, ``power``).  ``momentum`` defaults to 0.9, for ``"muon"`` to 0.95;
     ``ns_steps`` is Muon's."""
     if ns_steps is not None and name.lower() != "muon":
@@ -57,6 +58,10 @@ def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, mom
         if unknown or "kind" not in lr_schedule:
             raise ValueError(f"lr_schedule: a dict with 'kind', 'total_steps' and optionally 'warmup_steps', "
                              f"'min_ratio', 'power'; got keys {sorted(lr_schedule)}")
+    if ema is not None:
+        ema = dict(ema)
+        if set(ema) - {"decay", "warmup"} or "decay" not in ema:
+            raise ValueError(f"ema: a dict with 'decay' and optionally 'warmup'; got keys {sorted(ema)}")
     if trust_coefficient is not None and name not in ("lars", "lamb"):
         raise ValueError(f"trust_coefficient is for lars / lamb, not {name!r}")
     if name == "adam":
@@ -83,6 +88,8 @@ def build_optimizer(name: str, params, lr: float, weight_decay: float = 0.0, mom
         opt.set_grad_clip(clip_grad_norm, skip_nonfinite=skip_nonfinite)
     if lr_schedule is not None:
         opt.set_lr_schedule(lr_schedule.pop("kind"), **lr_schedule)
+    if ema is not None:
+        opt.set_ema(ema["decay"], warmup=bool(ema.get("warmup", False)))
     return opt
 
 

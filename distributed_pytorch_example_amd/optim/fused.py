@@ -26,11 +26,17 @@ A learning-rate schedule (``set_lr_schedule``: warm-up, then constant / linear /
 is evaluated on the device too: a one-block kernel turns a device step counter into this step's lr inside the
 hyper-parameter block, so no host copy happens per step and a captured step replays with an advancing lr.
 
+An exponential moving average of the weights (``set_ema``) is one more operand of the update kernels: they
+have the new weight in registers, so the average costs one load and one store per element, follows skipped
+steps, graph replays and per-bucket steps, and ``ema_weights()`` swaps it in (with the bf16 shadows) for
+validation.
+
 ``Muon`` (at the end of this file) shares the clip / schedule / state-dict machinery but has no GPU kernels yet:
 it runs its formulas in torch ops on CPU parameters and raises on GPU parameters.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import struct
 
@@ -62,6 +68,14 @@ def lr_factor(s: int, kind: str, warmup_steps: int, total_steps: int, min_ratio:
     if kind == "poly":
         return r + (1.0 - r) * (1.0 - t) ** power
     return 1.0
+
+
+def ema_decay_at(n: int, decay: float, warmup: bool = False) -> float:
+    """``d_n`` of ``set_ema``: the decay of the update made after ``n`` earlier ones, in Python floats (what
+    csrc/kernels/optim.hip's ema_decay_kernel evaluates on the device)."""
+    if n < 1:
+        return 0.0
+    return min(decay, (1.0 + n) / (10.0 + n)) if warmup else decay
 
 
 def _pack_desc(p, g, s1, s2, sh, n, group, ti):
@@ -99,6 +113,16 @@ class _FusedMixin:
         self._sched_cur = None  # fp32 [n_groups]: the lr of the last scheduled step
         self._sched_ran = False
         self._sched_last = 0  # the counter while there is no device block (CPU path, a freshly loaded state)
+        self._ema_cfg = None  # set_ema(): (decay, warmup)
+        self._ema_blk = None  # device EMA block (fp64): updates done, decay, warm-up on / off
+        self._ema_key = None
+        self._ema_cur = None  # fp32 [1]: the d_n of the last step
+        self._ema_ran = False
+        self._ema_last = 0  # the counter while there is no device block
+        self._ema_ptrs = None  # int64 [n_params] on the device: the averages' addresses, made with the table
+        self._ema_swapped = False  # inside ema_weights(): the parameters hold the average
+        self._swap_tab = None
+        self._swap_key = None
 
     # ------------------------------------------------------ learning-rate schedule
     def set_lr_schedule(self, kind, *, warmup_steps: int = 0, total_steps=None, min_ratio: float = 0.0,
@@ -200,8 +224,188 @@ class _FusedMixin:
             self._sched_last += 1
             self._sched_ran = True
 
+    # ------------------------------------------------------ weight EMA
+    def set_ema(self, decay, *, warmup: bool = False) -> None:
+        """Keep an exponential moving average of every parameter, updated inside every following ``step()``:
+        with ``n`` the updates already done and ``w`` the weights the step just wrote,
+
+            d_0 = 0 (the first update copies),  d_n = min(decay, (1 + n) / (10 + n)) if warmup else decay
+            ema = ema + (1 - d_n) (w - ema)                                    (fp32, per element)
+
+        -- ``torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay))`` called after
+        every step, parameters only (buffers such as BatchNorm's running statistics stay the live ones).
+        ``decay`` lies in [0, 1); ``None`` turns the average off and drops its state.  The average is the fp32
+        state tensor ``state[p]["ema"]``.  On GPU it is one more operand of the fused update kernel, ``1 - d_n``
+        comes from a device counter (``ema_num_updates``) that advances by the step's ok flag -- a step skipped
+        by ``skip_nonfinite`` makes no update and consumes no warm-up step -- and a captured step replays with
+        an advancing ``d_n``.  Setting it again keeps the average and the counter."""
+        if self._ema_swapped:
+            raise RuntimeError("set_ema: inside ema_weights() (the parameters hold the average)")
+        if decay is None:
+            if warmup:
+                raise ValueError("set_ema: warmup needs a decay")
+            if self._ema_cfg is not None:
+                self._tab = self._tab_key = None  # the next step rebuilds the table without the averages
+            self._ema_cfg = None
+            self._ema_ran = False
+            self._ema_ptrs = self._swap_tab = self._swap_key = None
+            self._ema_reset()
+            return
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"set_ema: decay must be in [0, 1), got {decay}")
+        if self._ema_cfg is None:
+            self._tab = self._tab_key = None  # the next step rebuilds the table with the averages
+        self._ema_cfg = (decay, bool(warmup))
+        if self._ema_blk is not None:
+            self._write_ema()  # device values: a captured step picks them up on replay
+
+    def _ema_reset(self):
+        """No average: drop the tensors, the counter restarts at 0 (whoever sets an EMA next starts afresh)."""
+        for st in self.state.values():
+            st.pop("ema", None)
+        self._ema_last = 0
+        if self._ema_blk is not None:
+            self._ema_blk[0].fill_(0.0)
+
+    @property
+    def ema_config(self):
+        """``{"decay", "warmup"}`` while an EMA is set, else ``None``."""
+        return None if self._ema_cfg is None else {"decay": self._ema_cfg[0], "warmup": self._ema_cfg[1]}
+
+    def _ema_block(self):
+        if self._ema_blk is None:
+            dev = self._all_params()[0].device
+            self._ema_blk = torch.zeros(3, dtype=torch.float64, device=dev)
+            self._ema_blk[0].fill_(float(self._ema_last))
+            self._ema_cur = torch.zeros(1, dtype=torch.float32, device=dev)
+            self._ema_key = None
+        return self._ema_blk
+
+    def _write_ema(self):
+        """decay and warm-up into the device block, when they changed."""
+        blk = self._ema_block()
+        if self._ema_cfg != self._ema_key:
+            blk[1:].copy_(torch.tensor([self._ema_cfg[0], 1.0 if self._ema_cfg[1] else 0.0], dtype=torch.float64))
+            self._ema_key = self._ema_cfg
+
+    def _ema_launch(self):
+        """1 - d_n into the hp rows (after the step's ok flag is final, before the update kernel, like the lr
+        schedule); the device counter advances by the ok flag."""
+        if self._ema_cfg is not None:
+            if self._ema_key is None:
+                self._write_ema()
+            ext().optim_ema_decay(self._hp, self._ema_blk, self._ema_cur)
+            self._ema_ran = True
+
+    @property
+    def ema_num_updates(self):
+        """0-d fp64 counter on the parameters' device: the EMA updates done."""
+        if self._ema_blk is not None:
+            return self._ema_blk[0]
+        ps = self._all_params()
+        if ps and ps[0].is_cuda:
+            return self._ema_block()[0]
+        return torch.tensor(float(self._ema_last), dtype=torch.float64)
+
+    @property
+    def ema_decay_now(self):
+        """0-d fp32 tensor on the parameters' device: the ``d_n`` of the last step.  ``None`` before the first
+        step with an EMA.  Reading it does not synchronise."""
+        return self._ema_cur[0] if self._ema_ran else None
+
+    def _ema_tensor(self, p):
+        st = self.state[p]
+        e = st.get("ema")
+        if e is None:
+            e = st["ema"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+        return e
+
+    def ema_parameters(self):
+        """The averages, in ``param_groups`` order (zeros before the first update)."""
+        if self._ema_cfg is None:
+            raise RuntimeError("ema_parameters: no EMA is set (set_ema)")
+        return [self._ema_tensor(p) for p in self._all_params()]
+
+    def _ema_live(self):
+        if self._ema_swapped:
+            raise RuntimeError("optimizer.step() inside ema_weights(): the parameters hold the average")
+
+    @torch.no_grad()
+    def _cpu_ema(self):
+        """CPU path, after an executed step: the same formula in torch ops (the first update copies, later
+        ones are ``lerp_(ema, w, 1 - d_n)``, which is AveragedModel's EMA bit for bit)."""
+        if self._ema_cfg is None:
+            return
+        d = ema_decay_at(self._ema_last, *self._ema_cfg)
+        for p in self._all_params():
+            e = self._ema_tensor(p)
+            if self._ema_last == 0:
+                e.copy_(p)
+            else:
+                e.lerp_(p, 1.0 - d)
+        self._ema_last += 1
+        self._ema_cur = torch.tensor([d], dtype=torch.float32)
+        self._ema_ran = True
+
+    @torch.no_grad()
+    def swap_ema(self) -> None:
+        """Exchange every parameter with its average, element for element (call it again to swap back: the
+        round trip is bitwise).  On GPU one multi-tensor kernel that also writes the bf16 shadows of the new
+        weights, followed by what a step does for derived shadows and cached filters.  ``step()`` refuses to
+        run in between."""
+        if self._ema_cfg is None:
+            raise RuntimeError("swap_ema: no EMA is set (set_ema)")
+        if int(self.ema_num_updates.item()) < 1:
+            raise RuntimeError("swap_ema: the average has had no update yet")
+        params = self._all_params()
+        if self._use_fused():
+            emas = [self._ema_tensor(p) for p in params]
+            shs = []
+            for p in params:
+                sh = getattr(p, "_dpe_shadow", None)
+                shs.append(sh if sh is not None and getattr(p, "_dpe_shadow_ver", -1) == p._version else None)
+            key = tuple((p.data_ptr(), e.data_ptr(), sh.data_ptr() if sh is not None else 0)
+                        for p, e, sh in zip(params, emas, shs))
+            if key != self._swap_key:
+                C = ext()
+                chunk = C.optim_chunk_size()
+                desc, chunks = bytearray(), []
+                for ti, (p, e, sh) in enumerate(zip(params, emas, shs)):
+                    if not (p.is_contiguous() and e.is_contiguous() and e.dtype == torch.float32 and e.numel() == p.numel()):
+                        raise RuntimeError("swap_ema needs contiguous parameters and fp32 averages of their size")
+                    desc += _pack_desc(p.data_ptr(), 0, 0, 0, sh.data_ptr() if sh is not None else 0, p.numel(), 0, ti)
+                    chunks += [(ti, c) for c in range((p.numel() + chunk - 1) // chunk)]
+                dev = params[0].device
+                self._swap_tab = (torch.frombuffer(desc, dtype=torch.uint8).to(dev),
+                                  torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(dev),
+                                  torch.tensor([e.data_ptr() for e in emas], dtype=torch.int64).to(dev))
+                self._swap_key = key
+            ext().optim_ema_swap(*self._swap_tab)
+            _state.after_optimizer_step()
+        else:
+            for p in params:
+                e = self._ema_tensor(p)
+                w = p.detach().clone()
+                p.copy_(e)
+                e.copy_(w)
+        self._ema_swapped = not self._ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with optimizer.ema_weights():`` -- the model computes with the averaged weights inside (validation,
+        exporting), and has its own back afterwards, bit for bit."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
     def state_dict(self):
         sd = super().state_dict()
+        if self._ema_cfg is not None:
+            n = int(self._ema_blk[0].item()) if self._ema_blk is not None else int(self._ema_last)
+            sd["ema"] = {"decay": self._ema_cfg[0], "warmup": self._ema_cfg[1], "num_updates": n}
         if self._sched_cfg is not None:
             kind, W, T, r, pw = self._sched_cfg
             last = int(self._sched[0].item()) if self._sched is not None else int(self._sched_last)
@@ -255,7 +459,9 @@ class _FusedMixin:
 
     @torch.no_grad()
     def _cpu_clip(self) -> bool:
-        """torch's own clip on the optimizer's parameters; False when the step is to be skipped."""
+        """torch's own clip on the optimizer's parameters; False when the step is to be skipped.  (Every CPU
+        step starts here: the place that refuses to step inside ``ema_weights()``.)"""
+        self._ema_live()
         if self._clip_max is None:
             return True
         params = self._all_params()
@@ -303,6 +509,8 @@ class _FusedMixin:
                     st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             if st.get("step") is None or st["step"].data_ptr() != self._steps[i].data_ptr():
                 st["step"] = self._steps[i]
+            if self._ema_cfg is not None:
+                self._ema_tensor(p)
 
     def _group_of(self, p):
         for g in self.param_groups:
@@ -334,6 +542,10 @@ class _FusedMixin:
             if sh is not None and getattr(p, "_dpe_shadow_ver", -1) != p._version:
                 sh = None  # stale shadow: let the layer re-cast it
             self._ti[id(p)] = ti
+            if self._ema_cfg is not None:
+                e = st["ema"]
+                if not (e.is_contiguous() and e.dtype == torch.float32 and e.numel() == p.numel() and e.device == p.device):
+                    raise RuntimeError("fused optimizer: state['ema'] must be a contiguous fp32 tensor of the parameter's size")
             desc += _pack_desc(p.data_ptr(), p.grad.data_ptr(), s1.data_ptr() if s1 is not None else 0,
                                s2.data_ptr() if s2 is not None else 0, sh.data_ptr() if sh is not None else 0,
                                p.numel(), gi_of[id(p)], ti)
@@ -346,6 +558,9 @@ class _FusedMixin:
         self._tab = (d, ck)
         self._chunks_host = chunks
         self._ov_cache = {}
+        self._ema_ptrs = None
+        if self._ema_cfg is not None:
+            self._ema_ptrs = torch.tensor([self.state[p]["ema"].data_ptr() for p in params], dtype=torch.int64).to(dev)
         if self._clip_max is not None:
             self._clip_part = torch.empty(max(len(chunks), 1), dtype=torch.float32, device=dev)
             self._clip_scratch()
@@ -370,9 +585,11 @@ class _FusedMixin:
             sh = getattr(p, "_dpe_shadow", None)
             s1 = st.get("exp_avg") if self._kind == 0 else st.get("momentum_buffer")
             s2 = st.get("exp_avg_sq") if self._kind == 0 else None
+            e = st.get("ema") if self._ema_cfg is not None else None
             ks.append((p.data_ptr(), p.grad.data_ptr() if p.grad is not None else 0,
                        sh.data_ptr() if sh is not None and getattr(p, "_dpe_shadow_ver", -1) == p._version else 0,
-                       s1.data_ptr() if s1 is not None else 0, s2.data_ptr() if s2 is not None else 0))
+                       s1.data_ptr() if s1 is not None else 0, s2.data_ptr() if s2 is not None else 0,
+                       e.data_ptr() if e is not None else 0))
         return tuple(ks)
 
     def load_state_dict(self, state_dict):
@@ -395,6 +612,24 @@ class _FusedMixin:
             if self._sched is not None:
                 self._sched[0].fill_(float(self._sched_last))
             self._sched_ran = False
+        es = state_dict.get("ema")
+        self._ema_swapped = False
+        self._swap_tab = self._swap_key = None
+        if es is not None:  # the checkpoint's average, settings and counter
+            self.set_ema(es["decay"], warmup=es["warmup"])
+            self._ema_last = int(es["num_updates"])
+            if self._ema_blk is not None:
+                self._ema_blk[0].fill_(float(self._ema_last))
+        else:  # a state without an average: an EMA set on this optimizer starts afresh
+            self._ema_reset()
+        self._ema_ran = False
+
+    def _step_kernel(self, d, ck):
+        """The plain update over chunk list ``ck``, with the EMA arm when one is set."""
+        if self._ema_cfg is not None:
+            ext().optim_step_ema(self._kind, d, ck, self._hp, self._steps, self._ema_ptrs)
+        else:
+            ext().optim_step(self._kind, d, ck, self._hp, self._steps)
 
     def _hp_row(self, g):
         raise NotImplementedError
@@ -435,7 +670,7 @@ class _FusedMixin:
                 self._tab[0].device)
             self._ov_cache[key] = ck
         with torch.cuda.stream(stream):
-            ext().optim_step(self._kind, self._tab[0], ck, self._hp, self._steps)
+            self._step_kernel(self._tab[0], ck)
         self._ov_done.update(key)
 
     @torch.no_grad()
@@ -444,6 +679,7 @@ class _FusedMixin:
         ``stream``, which the caller has already ordered after them.  The first bucket of an iteration
         refreshes the device table / hyper-parameters and advances every step counter once."""
         if not self._ov_open:
+            self._ema_live()
             with torch.cuda.stream(stream):
                 self._ensure_state()
                 key = self._key()
@@ -454,6 +690,9 @@ class _FusedMixin:
                 if self._sched_cfg is not None:
                     self._write_sched()
                     self._sched_launch()  # nothing grid-wide precedes the update here: ok is the host's 1.0
+                if self._ema_cfg is not None:
+                    self._write_ema()
+                    self._ema_launch()
                 self._steps.add_(1.0)
             self._ov_open, self._ov_done = True, set()
         tis = sorted({self._ti[id(p)] for p in params if id(p) in self._ti} - self._ov_done)
@@ -471,6 +710,7 @@ class _FusedMixin:
             self._ov_open = False
             _state.after_optimizer_step()
             return
+        self._ema_live()
         if not self.graph_safe or self._tab is None:
             self._ensure_state()
             key = self._key()
@@ -480,6 +720,8 @@ class _FusedMixin:
             self._write_hp()
             if self._sched_cfg is not None:
                 self._write_sched()
+            if self._ema_cfg is not None:
+                self._write_ema()
         d, ck = self._tab
         if self._trust is not None:
             self._trust_step(d, ck)
@@ -494,7 +736,8 @@ class _FusedMixin:
         else:
             self._steps.add_(1.0)
         self._sched_launch()
-        ext().optim_step(self._kind, d, ck, self._hp, self._steps)
+        self._ema_launch()
+        self._step_kernel(d, ck)
         _state.after_optimizer_step()
 
     # ------------------------------------------------------ layer-wise trust ratios (LARS / LAMB)
@@ -516,10 +759,14 @@ class _FusedMixin:
             self._clip_ran = True
         self._steps.add_(buf[2] if clip and self._clip_skip else 1.0)  # a skipped step advances no counter
         self._sched_launch()  # ok is final; LARS's update and LAMB's phase 2 (the readers of lr) come after
+        self._ema_launch()
         if self._trust == 1:
             C.optim_trust_partials(1, d, ck, self._hp, self._steps, pw, px)
         C.optim_trust_ratio(self._trust, d, first, nck, pw, px, self._hp, self._trust_stats)
-        C.optim_trust_step(self._trust, d, ck, self._hp, self._steps, self._trust_stats)
+        if self._ema_cfg is not None:
+            C.optim_trust_step_ema(self._trust, d, ck, self._hp, self._steps, self._trust_stats, self._ema_ptrs)
+        else:
+            C.optim_trust_step(self._trust, d, ck, self._hp, self._steps, self._trust_stats)
         self._trust_ran = True
 
     @property
@@ -585,10 +832,17 @@ class Adam(_FusedMixin, torch.optim.Adam):
         if not self._cpu_clip():
             return None
         base = self._cpu_sched_begin()
+        # torch's Adam initialises a parameter's state only while it is empty: an average made before the first step
+        # (ema_parameters()) steps aside for it
+        early = [(st, st.pop("ema")) for st in self.state.values() if len(st) == 1 and "ema" in st]
         try:
-            return super().step()
+            out = super().step()
         finally:
+            for st, e in early:
+                st["ema"] = e
             self._cpu_sched_end(base)
+        self._cpu_ema()
+        return out
 
 
 class AdamW(Adam):
@@ -628,9 +882,11 @@ class SGD(_FusedMixin, torch.optim.SGD):
             return None
         base = self._cpu_sched_begin()
         try:
-            return super().step()
+            out = super().step()
         finally:
             self._cpu_sched_end(base)
+        self._cpu_ema()
+        return out
 
 
 class LARS(SGD):
@@ -684,6 +940,7 @@ class LARS(SGD):
             self._cpu_update()
         finally:
             self._cpu_sched_end(base)
+        self._cpu_ema()
         return loss
 
     def _cpu_update(self):
@@ -756,6 +1013,7 @@ class LAMB(Adam):
             self._cpu_update()
         finally:
             self._cpu_sched_end(base)
+        self._cpu_ema()
         return loss
 
     def _cpu_update(self):
@@ -899,6 +1157,7 @@ class Muon(_FusedMixin, torch.optim.Optimizer):
             self._cpu_update()
         finally:
             self._cpu_sched_end(base)
+        self._cpu_ema()
         return loss
 
     def _cpu_update(self):

@@ -77,6 +77,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="gpt2 models: dropout rate in [0, 1) on the embedding sum, the attention probabilities (inside "
                         "the flash kernels, at the 8-bit rate round(256 p) / 256) and both residual branches; training "
                         "only (validation runs in eval mode); the mask state lives on the device and is not checkpointed")
+    p.add_argument("--ema-decay", type=float, default=None,
+                   help="keep an exponential moving average of the weights with this decay, in [0, 1), inside the optimizer "
+                        "step; every epoch validates a second time with the averaged weights and the checkpoints carry them "
+                        "in the optimizer state (default: off)")
+    p.add_argument("--ema-warmup", action="store_true",
+                   help="with --ema-decay: the decay of update n is min(decay, (1 + n) / (10 + n))")
     p.add_argument("--bucket-mb", type=float, default=None,
                    help="gradient bucket cap (default: the 7-link xGMI policy, parallel/buckets.py)")
     p.add_argument("--last-bucket-mb", type=float, default=None,
@@ -258,6 +264,10 @@ def main(argv=None):
         parser.error("--z-loss must be >= 0")
     if not 0.0 <= args.dropout < 1.0:
         parser.error("--dropout must be in [0, 1)")
+    if args.ema_warmup and args.ema_decay is None:
+        parser.error("--ema-warmup needs --ema-decay")
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay < 1.0:
+        parser.error("--ema-decay must be in [0, 1)")
     if args.dropout > 0.0 and not args.model.startswith("gpt2"):
         parser.error("--dropout needs a gpt2 model")
     ensure_single_process_env()
@@ -291,6 +301,7 @@ def main(argv=None):
     optimizer = build_optimizer(opt_name, model.parameters(), lr=args.lr, weight_decay=args.weight_decay,
                                 clip_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite_steps,
                                 lr_schedule=_lr_schedule_kw(parser, args, len(train_loader)),
+                                ema=None if args.ema_decay is None else {"decay": args.ema_decay, "warmup": args.ema_warmup},
                                 **({"trust_coefficient": args.trust_coefficient} if opt_name in ("lars", "lamb") else {}),
                                 **({"momentum": 0.95 if args.muon_momentum is None else args.muon_momentum,
                                     "ns_steps": 5 if args.muon_ns_steps is None else args.muon_ns_steps}
@@ -326,6 +337,16 @@ def main(argv=None):
         metrics /= world_size
         avg_train_loss, avg_val_loss, avg_val_accuracy = (v.item() for v in metrics)
 
+        # the averaged weights (set by --ema-decay or by the resumed checkpoint): a second validation with them
+        ema_on = optimizer.ema_config is not None and int(optimizer.ema_num_updates.item()) > 0
+        if ema_on:
+            with optimizer.ema_weights():
+                ema_metrics = torch.tensor(validate(model, val_loader, criterion, device, num_classes, args.max_steps, watchdog),
+                                           device=device)
+            pdist.all_reduce(ema_metrics, "sum")
+            ema_metrics /= world_size
+            ema_val_loss, ema_val_accuracy = (v.item() for v in ema_metrics)
+
         epoch_time = time.time() - epoch_start
         if rank == 0:
             logger.info(f"Epoch {epoch} completed in {epoch_time:.2f}s")
@@ -345,6 +366,9 @@ def main(argv=None):
             if getattr(optimizer, "current_lr", None) is not None:
                 logger.info("  LR (last step): " + ", ".join(f"{v:.6g}" for v in optimizer.current_lr.tolist())
                             + f", schedule step: {int(optimizer.schedule_step.item())}")
+            if ema_on:
+                logger.info(f"  EMA Val Loss: {ema_val_loss:.4f}, EMA Val Accuracy: {ema_val_accuracy:.2f}% "
+                            f"(decay {float(optimizer.ema_decay_now):.6g})")
             # no step heartbeat while rank 0 writes (RCCL async errors are still polled)
             with (watchdog.suspended() if watchdog is not None else _null()):
                 if avg_val_accuracy > best_accuracy:
