@@ -165,6 +165,50 @@ std::vector<Tensor> conv1x1_apply(const Tensor& x, const Tensor& w, const c10::o
   return {y, bits};
 }
 
+// The envelope of conv1x1_apply_cat: a 1x1 stride-1 downsample conv over xshape [N, H, W, Cin] (Cin in {64, 128})
+// beside a conv3 whose operand has cmid == Cin channels, both -> cout = 4 Cin.
+bool down_cat_ok(const std::vector<int64_t>& xshape, int64_t cmid, int64_t cout, int64_t stride) {
+  if (xshape.size() != 4 || stride != 1 || !pw_stream_on()) return false;
+  const int64_t M = xshape[0] * xshape[1] * xshape[2], C = xshape[3];
+  return (C == 64 || C == 128) && cmid == C && dpe_pw_cat_fwd_rowgroups(M, cout, C) > 0;
+}
+
+// y = relu(BN3(x' W^T) + BN_d(x2 W2^T)) of a downsample bottleneck's conv3 (x' = relu(x * in_coef) or x) and its
+// 1x1 stride-1 downsample conv over the block input x2, as ONE streaming pass over the concatenated K = [x' | x2]
+// (pwconv.hip PW_CAT): both BNs' coefficients are known in advance (bn_gram_coef), the two fp32 sums are scaled
+// per output channel and rounded once; neither pre-BN tensor exists.  Returns (y, ReLU bits of y).  The dynamic
+// schedule under a CU budget is built for both shapes, so the op has no fall-back of its own.
+std::vector<Tensor> conv1x1_apply_cat(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& in_coef,
+                                      const Tensor& out_coef, const Tensor& x2, const Tensor& w2, const Tensor& coef2) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(w); CHECK_CONTIG(w); CHECK_F32(out_coef); CHECK_CONTIG(out_coef);
+  CHECK_GPU(x2); CHECK_BF16(x2); CHECK_CONTIG(x2); CHECK_BF16(w2); CHECK_CONTIG(w2); CHECK_F32(coef2); CHECK_CONTIG(coef2);
+  const int64_t K1 = x.size(-1), M = x.numel() / K1, N = w.size(0), K2 = x2.size(-1);
+  TORCH_CHECK(x.dim() == 4 && K1 == K2 && x2.numel() == M * K2 && w.numel() == N * K1 && w2.numel() == N * K2 &&
+                  out_coef.numel() == 4 * N && coef2.numel() == 4 * N, "conv1x1_apply_cat: shapes");
+  if (has(in_coef)) {
+    CHECK_F32((*in_coef)); CHECK_CONTIG((*in_coef));
+    TORCH_CHECK(in_coef->numel() == 4 * K1, "conv1x1_apply_cat: in_coef must be the BN's [4][K] coefficients");
+  }
+  TORCH_CHECK(down_cat_ok(x2.sizes().vec(), K1, N, 1), "conv1x1_apply_cat: outside the envelope (down_cat_ok)");
+  const int rg = dpe_pw_cat_fwd_rowgroups(M, N, K2);
+  auto ysz = x.sizes().vec();
+  ysz.back() = N;
+  Tensor y = at::empty(ysz, x.options());
+  auto bsz = ysz;
+  bsz.back() = N / 8;
+  Tensor bits = at::empty(bsz, x.options().dtype(at::kByte));
+  dpe::PwArgs pa{};
+  pa.x = bp(x); pa.w = bp(w); pa.y = bpm(y);
+  pa.x2 = bp(x2); pa.w2 = bp(w2); pa.cat_k2 = (int)K2;
+  pa.in_coef = fpo(in_coef);
+  pa.out_coef = fp(out_coef);
+  pa.res_coef = fp(coef2);
+  pa.out_bits = (uint8_t*)bits.data_ptr();
+  pa.M = M; pa.N = N; pa.K = K1 + K2; pa.rg = rg; pa.sched = dpe_gemm::sched_buffer(cur_stream());
+  CHECK_RC(dpe_pw_launch(&pa, dpe::PW_CAT, cur_stream()), "pw_stream concatenated-K apply");
+  return {y, bits};
+}
+
 // BN3 backward by Gram algebra: from part (row 0: sum dz partials, [2][Cout][rg]), P = dz^T a2 [Cout][Cin], W,
 // u = W G, s, the forward coef: dgamma / dbeta / dw accumulate; returns the data grad's B operand
 // [Cout + Cin][Cin] bf16 (= [diag(a) W ; W^T diag(b) W]) and its bias c^T W [Cin].
@@ -642,6 +686,11 @@ void register_bn(pybind11::module& m) {
   m.def("conv1x1_apply", &conv1x1_apply, py::arg("x"), py::arg("w"), py::arg("in_coef"), py::arg("out_coef"),
         py::arg("residual"), py::arg("res_coef") = py::none(),
         "y = relu(BN(x' W^T) + residual [BN_d]) and its ReLU bits (pre-BN tensor never stored)");
+  m.def("conv1x1_apply_cat", &conv1x1_apply_cat, py::arg("x"), py::arg("w"), py::arg("in_coef"), py::arg("out_coef"),
+        py::arg("x2"), py::arg("w2"), py::arg("coef2"),
+        "y = relu(BN3(x' W^T) + BN_d(x2 W2^T)) over the concatenated K and its ReLU bits (no pre-BN tensors)");
+  m.def("down_cat_ok", &down_cat_ok, py::arg("xshape"), py::arg("cmid"), py::arg("cout"), py::arg("stride"),
+        "conv1x1_apply_cat's envelope: 1x1 stride-1 downsample conv, Cin == cmid in {64, 128}, cout == 4 Cin");
   m.def("bn_gram_bwd", &bn_gram_bwd, py::arg("part"), py::arg("P"), py::arg("w"), py::arg("u"), py::arg("s"),
         py::arg("coef"), py::arg("gamma"), py::arg("M"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dw"),
         "BN3 backward from (sum dz partials, P = dz^T a2): dgamma/dbeta/dw +=, returns (B_cat bf16, bias)");

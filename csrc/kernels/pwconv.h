@@ -11,6 +11,10 @@ enum PwEpi : int {
   PW_APPLY = 2,  // y = relu(BN(x . W^T) + residual): out_coef = the BN's [4][N] coefficients, known before the
                  // conv (Gram algebra, bngram.hip); the pre-BN tensor is never stored; out_bits = ReLU bits of y
   PW_DSUM = 3,   // PW_DGRAD with st_mask and no st_x: stats row 0 = sum dz only (row 1 left unwritten)
+  PW_CAT = 4,    // y = relu(out_coef.scale * (x' . W^T) + res_coef.scale * (x2 . W2^T) + out_coef.shift + res_coef.shift)
+                 // over the concatenated K = [x' | x2] (x' = relu(x * in_coef) or x; K = 2 cat_k2): a bottleneck's conv3 +
+                 // BN3 and its 1x1 stride-1 downsample conv + BN_d in one pass, both BNs' coefficients known before the
+                 // convs (Gram algebra); neither pre-BN tensor is stored; out_bits = ReLU bits of y
 };
 
 struct PwArgs {
@@ -39,6 +43,10 @@ struct PwArgs {
   const float* p_coef;       // [4][p_k2]: the operand is bf16(relu(p_src * scale + shift)); nullptr = plain
   float* p_slab;             // [rg][N][p_k2] fp32: one partial product per row group (dpe_pw_p_reduce sums them)
   int p_k2;
+  // PW_CAT: the second K segment (plain operand), cat_k2 = K / 2 channels; x and w then hold K - cat_k2 channels
+  const uint16_t* x2;        // [M][cat_k2] bf16
+  const uint16_t* w2;        // [N][cat_k2] bf16
+  int cat_k2;
 };
 
 // The concatenated-K data grad of the Gram-path BN3 backward (bngram.hip) on a streaming kernel:
@@ -71,6 +79,10 @@ extern "C" int dpe_pw_cat_launch(const dpe::PwCatArgs* args, int64_t K1, int64_t
 // rows and the last two thirds are claimed at run time (PwArgs::sched); otherwise one per resident block row.
 extern "C" int dpe_pw_rowgroups(int64_t M, int64_t N, int64_t K, int epi);
 extern "C" int dpe_pw_launch(const dpe::PwArgs* args, int epi, hipStream_t stream);
+
+// PW_CAT: row groups of the launch for two segments of k2 channels each (K = 2 k2), or 0 outside its envelope
+// (k2 in {64, 128}, N = 4 k2).  The launch is dpe_pw_launch with K = 2 k2, cat_k2 = k2 and rg from here.
+extern "C" int dpe_pw_cat_fwd_rowgroups(int64_t M, int64_t N, int64_t k2);
 
 // PW_DSUM with the fused product (PwArgs::p_src): row groups of that launch, or 0 outside its envelope
 // ((K, k2) in {(64, 64), (128, 64), (128, 128)} inside PW_DSUM's own).  The launch is dpe_pw_launch with

@@ -97,13 +97,20 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   constexpr int STG = 32 * ROWB;
   // stores outstanding per wave per tile, for the counted vmcnt below (the epilogue's operand
   // loads are consumed -- waited for -- inside the tile, so they are not outstanding here)
-  constexpr int S = (EPI == PW_APPLY ? 4 : 2) * NPS;  // (PW_APPLY: the y chunk and its ReLU-mask byte)
+  constexpr int S = (EPI == PW_APPLY || EPI == PW_CAT ? 4 : 2) * NPS;  // (PW_APPLY / PW_CAT: the y chunk and its ReLU-mask byte)
   constexpr int VM = (NS - 1) * S + (NS - 2) * P;
   static_assert(VM < 64, "vmcnt range");
   // ONE LDS object: ring, staging, in_coef's [scale | shift] of the K input channels, the claim slot.  (With a
   // second __shared__ object the compiler cannot tell the ring DMA's LDS writes from the other accesses and
   // drains vmcnt(0) -- the next tile's DMA -- before each tile's fragment reads.)
-  constexpr bool PF = K2 > 0;
+  // PW_CAT: the K input channels are two concatenated segments of K2 = K / 2 each -- a.x (BN + ReLU on load by
+  // in_coef) and the plain a.x2, with weights a.w / a.w2 [N][K2] -- accumulated separately and combined per output
+  // channel in the epilogue.  Waves 0-1 DMA the first segment's K chunks of a tile, waves 2-3 the second's.
+  constexpr bool CAT = EPI == PW_CAT;
+  static_assert(!CAT || (WN == 32 && 2 * K2 == K && K2 % 64 == 0), "concatenated K: envelope");
+  constexpr int KS = CAT ? K2 : K;            // channels (row pitch) of a streamed operand
+  constexpr int KC1 = KS / 32;                // K chunks of the first segment
+  constexpr bool PF = K2 > 0 && !CAT;
   static_assert(!PF || (EPI == PW_DSUM && WN == 32 && (K2 == 64 || K2 == 128) && K2 <= K), "fused P: envelope");
   // (PF: + the a2 image [64 rows][K2] bf16, 16-B chunk c of row r at c ^ 2 h(r) -- bngram.hip's layout)
   constexpr int A2OFF = NS * TILE + 4 * STG + 2 * K * 4 + 16, A2RB = 2 * (PF ? K2 : 8);
@@ -137,7 +144,10 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int n = n0w + 16 * ni + li, k0 = 32 * kc + 8 * g;
-      if constexpr (!DG) {
+      if constexpr (CAT) {
+        const uint16_t* const ws = kc < KC1 ? a.w : a.w2;
+        wf[ni][kc] = __builtin_bit_cast(bf16x8, *(const u32x4*)(ws + (int64_t)n * KS + (k0 - (kc < KC1 ? 0 : KS))));
+      } else if constexpr (!DG) {
         wf[ni][kc] = __builtin_bit_cast(bf16x8, *(const u32x4*)(a.w + (int64_t)n * K + k0));
       } else {  // W stored [K][N]: gather the column (once per block)
         s16x8 v;
@@ -160,17 +170,19 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   }
 
   // DMA pieces: piece q (of 4P per tile) = K chunk q / 4, rows 16 (q % 4) .. +15; lane -> (row, 16-B chunk)
-  const __amdgpu_buffer_rsrc_t xr = rsrc(a.x, (uint32_t)((int64_t)M * K * 2));
+  // (PW_CAT: the wave's segment -- wave-uniform, so one resource per wave)
+  const bool seg2 = CAT && wid >= 2;
+  const __amdgpu_buffer_rsrc_t xr = rsrc(seg2 ? a.x2 : a.x, (uint32_t)((int64_t)M * KS * 2));
   uint32_t voff[P];
 #pragma unroll
   for (int i = 0; i < P; ++i) {
     const int q = wid * P + i, kc = q >> 2, row = (q & 3) * 16 + (lane >> 2);
     const int lc = (lane & 3) ^ ((0x78 >> (((row >> 2) & 3) << 1)) & 3);
-    voff[i] = (uint32_t)(row * K * 2 + kc * 64 + lc * 16);
+    voff[i] = (uint32_t)(row * KS * 2 + (kc % KC1) * 64 + lc * 16);
   }
   auto issue = [&](int t, int slot) {
     char* dst = smem + slot * TILE;
-    const int64_t base = t >= 0 ? (int64_t)t * BM * K * 2 : 0;
+    const int64_t base = t >= 0 ? (int64_t)t * BM * KS * 2 : 0;
     const int valid_rows = t >= 0 ? M - t * BM : 0;  // rows past M (or t < 0: no tile) read as zeros
 #pragma unroll
     for (int i = 0; i < P; ++i) {
@@ -229,12 +241,26 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   const __amdgpu_buffer_rsrc_t rmrs = rsrc(a.res_mask, a.res_mask ? mbytes : 0u);
   const __amdgpu_buffer_rsrc_t xsrs = rsrc(a.st_x, bnx ? ybytes : 0u);
   const __amdgpu_buffer_rsrc_t smrs = rsrc(a.st_mask, (bnb && a.st_mask) ? mbytes : 0u);
-  const __amdgpu_buffer_rsrc_t obrs = rsrc(a.out_bits, (EPI == PW_APPLY && a.out_bits) ? mbytes : 0u);
+  const __amdgpu_buffer_rsrc_t obrs = rsrc(a.out_bits, ((EPI == PW_APPLY || CAT) && a.out_bits) ? mbytes : 0u);
   const __amdgpu_buffer_rsrc_t psrs = rsrc(a.p_src, PF ? (uint32_t)((int64_t)M * K2 * 2) : 0u);
 
   if (!DG && a.in_coef) {  // before the ring's first DMA (its counted waits start after this)
-    for (int i = tid; i < 2 * K; i += 256) bnin[i] = a.in_coef[i];
+    for (int i = tid; i < 2 * KS; i += 256) bnin[i] = a.in_coef[i];
     __syncthreads();
+  }
+  // PW_CAT: the lane's output channels in the accumulator layout (n0w + 16 ni + 4 g + e): BN3's scale on the first
+  // segment's sums, BN_d's on the second's, and the two shifts as one bias
+  float c1s[CAT ? NI : 1][4], c2s[CAT ? NI : 1][4], cbs[CAT ? NI : 1][4];
+  if constexpr (CAT) {
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int n = n0w + 16 * ni + 4 * g + e;
+        c1s[ni][e] = a.out_coef[n];
+        c2s[ni][e] = a.res_coef[n];
+        cbs[ni][e] = a.out_coef[N + n] + a.res_coef[N + n];
+      }
   }
   if constexpr (PF) {  // a2's [scale | shift] in the (data grad: otherwise unused) table
     if (a.p_coef)
@@ -251,10 +277,11 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
     // stage's DMAs, so the compiler's wait for them leaves the ring's counted vmcnt intact.  The
     // wider-WN tiles have no registers for it (they would spill).
     constexpr bool HOIST = (EPI != PW_FWD) && (WN == 32);
-    constexpr int HN = HOIST ? NPS : 1;
+    constexpr bool HLD = HOIST && !CAT;  // (PW_CAT: unconditional buffer stores as the hoisted forms, no operand loads)
+    constexpr int HN = HLD ? NPS : 1;
     u32x4 hrv[2][HN], hxv[2][HN];
     uint32_t hrmb[2][HN], hsmb[2][HN];
-    if constexpr (HOIST) {
+    if constexpr (HLD) {
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
@@ -294,12 +321,12 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
       // values that are never stored and kept out of the statistics.
       char* timg = smem + cur_slot * TILE;
 #pragma unroll
-      for (int q = 0; q < TILE / 16 / 256; ++q) {
+      for (int q = 0; q < BM * KS * 2 / 16 / 256; ++q) {  // (PW_CAT: the first segment's K chunks only)
         const int c = q * 256 + tid, kc = c / (BM * 4), rem = c % (BM * 4), row = rem >> 2, pc = rem & 3;
         const int lc = pc ^ ((0x78 >> (((row >> 2) & 3) << 1)) & 3);
         u32x4* pch = (u32x4*)(timg + kc * (BM * 64) + row * 64 + pc * 16);
         const f32x4* cs = (const f32x4*)(bnin + 32 * kc + 8 * lc);
-        const f32x4* chh = (const f32x4*)(bnin + K + 32 * kc + 8 * lc);
+        const f32x4* chh = (const f32x4*)(bnin + KS + 32 * kc + 8 * lc);
         const f32x4 s0 = cs[0], s1 = cs[1], h0 = chh[0], h1 = chh[1];
         const float sc8[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
         const float sh8[8] = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
@@ -319,6 +346,13 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc2[CAT ? MI : 1][CAT ? NI : 1];  // PW_CAT: the second segment's sums
+    if constexpr (CAT) {
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) acc2[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       bf16x8 xf[MI];
@@ -327,8 +361,15 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
+        for (int ni = 0; ni < NI; ++ni) {
+          if constexpr (CAT) {
+            if (kc >= KC1) {
+              acc2[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni][kc], xf[mi], acc2[mi][ni], 0, 0, 0);
+              continue;
+            }
+          }
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni][kc], xf[mi], acc[mi][ni], 0, 0, 0);
+        }
     }
     if constexpr (PF) {
       // the a2 image, once per block, in place: everything older than the P ring DMAs just issued has landed
@@ -364,7 +405,7 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
       // the half's epilogue operands first: their latency overlaps the staging below
       u32x4 rv[NPS], xv[NPS];
       uint32_t rmb[NPS], smb[NPS];
-      if constexpr (HOIST) {
+      if constexpr (HLD) {
 #pragma unroll
         for (int ps = 0; ps < HN; ++ps) {
           rv[ps] = hrv[hf][ps];
@@ -391,6 +432,12 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
         const int mi = 2 * hf + mh;
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
+          if constexpr (CAT) {
+            // relu(scale3 * sum1 + scale_d * sum2 + shift3 + shift_d) from the fp32 sums: ONE rounding, of the output
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              acc[mi][ni][e] = fmaxf(fmaf(acc[mi][ni][e], c1s[ni][e], fmaf(acc2[mi][ni][e], c2s[ni][e], cbs[ni][e])), 0.f);
+          }
           u32x2 pk;
           pk[0] = pack_bf2(acc[mi][ni][0], acc[mi][ni][1]);
           pk[1] = pack_bf2(acc[mi][ni][2], acc[mi][ni][3]);
@@ -400,7 +447,7 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
       // the hoisted epilogue operands (both halves): everything but the P ring DMAs issued after them has
       // landed.  (The DMA issue is unconditional, so P younger ops exist on every path; with this counted
       // wait the compiler needs no wait of its own for the conditionally loaded operands.)
-      if (HOIST && hf == 0) wait_vm<P>();
+      if (HLD && hf == 0) wait_vm<P>();
 #pragma unroll
       for (int ps = 0; ps < NPS; ++ps) {
         const int row = ps * RPP + lane / CPRW;
@@ -425,6 +472,9 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
             __builtin_amdgcn_raw_buffer_store_b8(relu_mask_byte(v), obrs, valid ? (uint32_t)(((int64_t)m * N + nch) >> 3) : OOB, 0, 0);
           else if (valid && a.out_bits)
             a.out_bits[((int64_t)m * N + nch) >> 3] = relu_mask_byte(v);
+        } else if constexpr (CAT) {
+          // (v is the block output already; its bits are the bits of the stored bf16 value)
+          __builtin_amdgcn_raw_buffer_store_b8(relu_mask_byte(v), obrs, valid ? (uint32_t)(((int64_t)m * N + nch) >> 3) : OOB, 0, 0);
         } else if constexpr (EPI == PW_FWD) {
           // statistics of the stored (rounded) values (rows past M: zeros, or relu(shift) terms
           // with in_coef -- masked)
@@ -502,7 +552,7 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   // statistics: reduce over the lanes holding the same channel chunk (lane = row * CPRW + ch),
   // one partial column per row group
   auto flush_stats = [&](int col) {
-    if (EPI != PW_APPLY && a.stats) {
+    if (EPI != PW_APPLY && !CAT && a.stats) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
 #pragma unroll
@@ -874,7 +924,7 @@ extern "C" int dpe_pw_cat_launch(const PwCatArgs* args, int64_t K1, int64_t K2, 
 #define DPE_PW128_FWD_WN 64
 #endif
 static int pw_wn(int K, int epi) {
-  if (epi == PW_APPLY) return 32;  // epilogue operand (the residual) hoisted ahead of the MFMAs, as the data grads
+  if (epi == PW_APPLY || epi == PW_CAT) return 32;  // epilogue operand (the residual) hoisted ahead of the MFMAs, as the data grads
   if (epi == PW_DSUM) epi = PW_DGRAD;
   if (K == 64) return epi == PW_DGRAD ? DPE_PW64_DGRAD_WN : DPE_PW64_FWD_WN;
   if (K == 128) return epi == PW_FWD ? DPE_PW128_FWD_WN : 32;
@@ -927,8 +977,16 @@ static int pw_cap_p(int64_t K, int64_t k2) {
   return 0;
 }
 
+// the concatenated-K forward (PW_CAT): two segments of k2 channels
+static bool pw_cat_shape(int64_t K, int64_t k2) { return (K == 128 && k2 == 64) || (K == 256 && k2 == 128); }
+template <bool DYN>
+static int pw_cap_cat(int64_t K) {
+  return K == 128 ? pw_slots<128, 32, 3, PW_CAT, DYN, 64>() : pw_slots<256, 32, 2, PW_CAT, DYN, 128>();
+}
+
 template <bool DYN>
 static int pw_cap(int64_t K, int epi, int64_t k2 = 0) {
+  if (epi == PW_CAT) return pw_cap_cat<DYN>(K);
   if (k2 > 0) return pw_cap_p<DYN>(K, k2);
   return epi == PW_FWD ? pw_capacity<PW_FWD, DYN>((int)K)
                        : epi == PW_APPLY ? pw_capacity<PW_APPLY, DYN>((int)K)
@@ -942,9 +1000,13 @@ static int pw_cap(int64_t K, int epi, int64_t k2 = 0) {
 // (>= NS + 3: the stream claims the next row group NS + 2 tiles before the current one ends).
 struct PwPlan { int rg, srg; };
 static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi, int64_t k2 = 0) {
-  if (k2 > 0 && (epi != PW_DSUM || !pw_p_shape(K, k2))) return {0, 0};
+  if (epi == PW_CAT) {
+    if (!pw_cat_shape(K, k2)) return {0, 0};
+  } else if (k2 > 0 && (epi != PW_DSUM || !pw_p_shape(K, k2))) {
+    return {0, 0};
+  }
   if (K != 64 && K != 128 && K != 256) return {0, 0};
-  if (epi != PW_FWD && epi != PW_DGRAD && epi != PW_APPLY && epi != PW_DSUM) return {0, 0};
+  if (epi != PW_FWD && epi != PW_DGRAD && epi != PW_APPLY && epi != PW_DSUM && epi != PW_CAT) return {0, 0};
   const int bnb = 4 * pw_wn((int)K, epi);
   if (N % bnb || N < 2 * K) return {0, 0};  // write-heavy shapes only (N >= 2K)
   if (M * K * 2 >= (1ll << 31) - 4096 || M * N >= (1ll << 31) - 256) return {0, 0};
@@ -954,7 +1016,7 @@ static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi, int64_t k2 = 0) 
   if (reserve > 0 && pw_dynamic()) {
     // fused P with 128 columns has no dynamic variant (registers): outside the envelope while a CU budget
     // is in force -- the caller takes the separate weight grad
-    if (k2 == 128) return {0, 0};
+    if (k2 == 128 && epi != PW_CAT) return {0, 0};
     const int64_t srg = std::max<int64_t>(1, (pw_cap<true>(K, epi, k2) - reserve) / nbN);
     // (an eighth static, the rest claimed: a block two or three times slower than its peers -- a
     // VALU-bound foreign wave on its SIMD -- ends its static row group well before the launch's end, and
@@ -971,6 +1033,10 @@ static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi, int64_t k2 = 0) 
 }
 
 extern "C" int dpe_pw_rowgroups(int64_t M, int64_t N, int64_t K, int epi) { return pw_plan(M, N, K, epi).rg; }
+
+extern "C" int dpe_pw_cat_fwd_rowgroups(int64_t M, int64_t N, int64_t k2) {
+  return (k2 > 0 && N == 4 * k2) ? pw_plan(M, N, 2 * k2, PW_CAT, k2).rg : 0;
+}
 
 extern "C" int dpe_pw_p_rowgroups(int64_t M, int64_t N, int64_t K, int64_t k2) {
   return k2 > 0 ? pw_plan(M, N, K, PW_DSUM, k2).rg : 0;
@@ -1013,7 +1079,12 @@ extern "C" int dpe_pw_p_reduce(const float* slab, int rg, int64_t n, float* P, h
 extern "C" int dpe_pw_launch(const PwArgs* args, int epi, hipStream_t st) {
   const PwArgs& a = *args;
   if (a.p_k2 < 0 || (a.p_k2 > 0 && (epi != PW_DSUM || !a.p_src || !a.p_slab))) return -1;
-  if (a.rg <= 0 || a.rg != pw_plan(a.M, a.N, a.K, epi, a.p_k2).rg) return -1;
+  if ((epi == PW_CAT) != (a.cat_k2 > 0) || (epi == PW_CAT && a.p_k2 > 0)) return -1;
+  const int64_t k2 = epi == PW_CAT ? a.cat_k2 : a.p_k2;
+  if (a.rg <= 0 || a.rg != pw_plan(a.M, a.N, a.K, epi, k2).rg) return -1;
+  if (epi == PW_CAT && (!a.x2 || !a.w2 || !a.out_coef || !a.res_coef || !a.out_bits || a.residual || a.st_x || a.stats ||
+                        a.res_h > 0))
+    return -1;
   if (epi == PW_FWD && (a.residual || a.st_x)) return -1;
   if (a.st_x && !a.st_coef) return -1;
   if (epi == PW_DSUM && (a.st_x || !a.st_mask || !a.stats)) return -1;
@@ -1022,7 +1093,7 @@ extern "C" int dpe_pw_launch(const PwArgs* args, int epi, hipStream_t st) {
     return -1;
   // resident row groups: all of them, or (CU budget in force) the first half, the rest claimed
   // (no claim counters -- a stream being captured: the static variant over all rg row groups)
-  const int srg = a.sched ? pw_plan(a.M, a.N, a.K, epi, a.p_k2).srg : a.rg;
+  const int srg = a.sched ? pw_plan(a.M, a.N, a.K, epi, k2).srg : a.rg;
   const bool dyn = srg < a.rg;
   const int wn = pw_wn((int)a.K, epi);
   const dim3 grid((unsigned)(srg * (a.N / (4 * wn)))), block(256);
@@ -1037,6 +1108,16 @@ extern "C" int dpe_pw_launch(const PwArgs* args, int epi, hipStream_t st) {
     if (dyn) hipLaunchKernelGGL((pw::pw_stream_kernel<K_, 32, NS_, PW_DSUM, true, K2_>), grid, block, 0, st, a);  \
     else hipLaunchKernelGGL((pw::pw_stream_kernel<K_, 32, NS_, PW_DSUM, false, K2_>), grid, block, 0, st, a);     \
     return 0;                                                                                              \
+  }
+  if (epi == PW_CAT) {
+    if (a.K == 128) {
+      if (dyn) hipLaunchKernelGGL((pw::pw_stream_kernel<128, 32, 3, PW_CAT, true, 64>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((pw::pw_stream_kernel<128, 32, 3, PW_CAT, false, 64>), grid, block, 0, st, a);
+    } else {
+      if (dyn) hipLaunchKernelGGL((pw::pw_stream_kernel<256, 32, 2, PW_CAT, true, 128>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((pw::pw_stream_kernel<256, 32, 2, PW_CAT, false, 128>), grid, block, 0, st, a);
+    }
+    return 0;
   }
   if (a.p_k2 > 0) {
     PW_GO_P(64, 4, 64) PW_GO_P(128, 3, 64)

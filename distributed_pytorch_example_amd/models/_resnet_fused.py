@@ -70,6 +70,18 @@ epilogue emits the sum-dz partials only (it reads no hd).  The forward's outputs
 segment over x[:, ::2, ::2] by row addressing and hands conv1's streaming data grad the compact [N, H/2, W/2, Cin]
 grid to add at the even pixels.
 
+The downsample conv folded into conv3 (DPE_DOWN_CAT=1, default; the stride-1 blocks above -- ResNet-50's layer1.0 --
+in the training forward): BN_d's FORWARD statistics follow from the same (G_x, s_x) and W_d, exactly as BN3's follow
+from (G, s, W3), so bn_gram_coef yields BN_d's coefficients (scale, shift, mean, invstd; running statistics updated
+with the unbiased variance) and u_d before any conv runs, and the block output
+    out = relu([a2 | x] . [diag(scale3) W3 | diag(scale_d) W_d]^T + shift3 + shift_d)
+is ONE streaming pass over the concatenated K (conv1x1_apply_cat; pwconv.hip PW_CAT: a2 = relu(BN2(h2)) on load as
+today, two fp32 accumulator sets scaled per output channel in the epilogue, one rounding, the ReLU bits of the stored
+value).  hd is neither written nor read, the downsample conv and BN_d's bn_finalize are not launched, and the Gram
+pass over x and its pilot run before conv3.  The static and the dynamic-schedule kernels are both built, so under a
+CU budget the path stays as it is (no fall-back to the separate calls is needed).  Eval / no-grad forwards,
+defer_out / DPE_AX_FWD and the non-Gram paths are unchanged; DPE_DOWN_CAT=0 makes today's calls bit for bit.
+
 Weight gradients are accumulated straight into the DDP bucket views and each
 parameter is announced to the reducer as soon as its gradient is final, in
 reverse-forward order, so bucket all-reduces start while earlier blocks are
@@ -136,6 +148,17 @@ _BND_GRAM_S2 = _BND_GRAM and os.environ.get("DPE_BND_GRAM_S2", "0") == "1"
 # pw_dgrad_fused_p_ok holds -- bottleneck widths 64 / 128 behind a 64- or 128-wide conv1 (ResNet-50: layer1.0 to
 # layer1.2, layer2.1 and layer2.2).  Measurements: docs/perf_notes.md.
 _PW_FUSED_P = _GRAM and os.environ.get("DPE_PW_FUSED_P", "1") != "0"
+# DPE_DOWN_CAT=0: the downsample conv of a BND_GRAM block as its own pass (hd written, BN_d's statistics from its
+# epilogue + bn_finalize, hd read back as conv3's residual; bit for bit the calls before the fused form; A/B
+# reference).  On: BN_d's forward coefficients from the Gram pass over x (bn_gram_coef, which also yields u_d) and
+# the downsample conv inside conv3's streaming pass over the concatenated K [a2 | x] (conv1x1_apply_cat, pwconv.hip
+# PW_CAT) where down_cat_ok holds -- stride-1 1x1 downsample convs with 64 / 128 input channels beside an equally
+# wide conv3 operand (ResNet-50: layer1.0).  Training forward only.  Both the static and the dynamic-schedule
+# kernels are built, so a CU budget needs no fall-back to the separate calls.  Measurements: docs/perf_notes.md.
+# The block's OUTPUT does not depend on which backward form BN_d takes: where the fused forward applies but BN_d's
+# Gram backward does not (bnd_gram_ok fails, or the switch is flipped in-process for an A/B of the backward alone),
+# the forward is the same fused pass and hd is produced beside it for the backward only.
+_DOWN_CAT =_BND_GRAM and os.environ.get("DPE_DOWN_CAT", "1") != "0"
 
 
 def _ax_ok(conv, cin) -> bool:
@@ -220,11 +243,31 @@ class BottleneckFn(Function):
                                 bn.eps)
 
         c1conv, c2conv = convs[0].conv, convs[1].conv
-        if h1_st is None and block.down is not None:
+        h1_shape = [x.shape[0], _out_hw(x.shape[1], c1conv), _out_hw(x.shape[2], c1conv), c1conv.out_channels]
+        h2_shape = [x.shape[0], _out_hw(h1_shape[1], c2conv), _out_hw(h1_shape[2], c2conv), c2conv.out_channels]
+        out_shape = [*h2_shape[:3], convs[2].conv.out_channels]
+        dconv = block.down.conv if block.down is not None else None
+        # BN3 by Gram algebra (below): decided from the shapes alone.  gram_next < 0: the successor is a downsample
+        # block, which chains this block's BN3 backward only when its strided conv1 data grad can take the residual
+        # (the successor's own strided_ok test)
+        use_gram = bool(gram_next and link_out is not None and not defer_out and h1_st is None
+                        and (gram_next > 0 or C.pw_dgrad_strided_residual_ok(out_shape, -gram_next))
+                        and C.gram_ok(h2_shape, convs[2].conv.out_channels, abs(gram_next)))
+        # ... and with it the downsample BN's backward (DPE_BND_GRAM)
+        bnd_gram = bool(use_gram and _BND_GRAM and dconv is not None and tuple(dconv.kernel_size) == (1, 1)
+                        and tuple(dconv.padding) == (0, 0)
+                        and C.bnd_gram_ok(list(x.shape), dconv.out_channels, list(dconv.stride))
+                        and (tuple(dconv.stride) == (1, 1) or (_BND_GRAM_S2 and tuple(c1conv.stride) == (1, 1) and
+                             C.pw_dgrad_strided_residual_ok(list(x.shape), c1conv.out_channels))))
+        # ... and the downsample conv folded into conv3's pass (DPE_DOWN_CAT): no hd tensor at all
+        # (a forward property: it does not ask which backward form BN_d takes -- see _DOWN_CAT)
+        down_cat = bool(use_gram and _DOWN_CAT and dconv is not None and tuple(dconv.kernel_size) == (1, 1)
+                        and tuple(dconv.padding) == (0, 0) and tuple(dconv.stride) == (1, 1)
+                        and C.down_cat_ok(list(x.shape), h2_shape[3], dconv.out_channels, 1))
+        if h1_st is None and block.down is not None and not down_cat:
             hd, cd = conv_coef(3, x)  # BN_d is applied inside BN3's pass (bn_apply with residual_coef)
         else:
-            hd, cd = None, None  # (x still pending: after conv1 has written it)
-        h1_shape = [x.shape[0], _out_hw(x.shape[1], c1conv), _out_hw(x.shape[2], c1conv), c1conv.out_channels]
+            hd, cd = None, None  # (x still pending: after conv1 has written it; or hd never exists: down_cat)
         if _ROW_BNIN and C.row_bn_on_load(h1_shape, list(ws[1].shape), *_conv_conf(c2conv)):
             # a1 never materialised: conv2 applies relu(BN1(h1)) to its input rows on load
             h1, c1 = conv_coef(0, x)
@@ -249,12 +292,8 @@ class BottleneckFn(Function):
         want_bits = True  # 1/16 of out: read by the next block's fused epilogue or by this block's BN3 backward
         gram = None
         bnd = None  # (u_d, s_x): the downsample BN's backward runs by Gram algebra
-        # gram_next < 0: the successor is a downsample block, which chains this block's BN3 backward only
-        # when its strided conv1 data grad can take the residual (the successor's own strided_ok test)
-        out_shape = [*h2.shape[:3], convs[2].conv.out_channels]
-        if (gram_next and link_out is not None and not defer_out and h1_st is None
-                and (gram_next > 0 or C.pw_dgrad_strided_residual_ok(out_shape, -gram_next))
-                and C.gram_ok(list(h2.shape), convs[2].conv.out_channels, abs(gram_next))):
+        assert list(h2.shape) == h2_shape
+        if use_gram:
             # BN3 statistics from G = a2^T a2, s = colsum(a2); conv3 writes relu(BN3(h3) + idn) directly
             src, src_coef = (h2, c2) if a2 is None else (a2, None)
             G, sv = C.bn_gram(src, src_coef, c2)  # centred on a pilot shift from BN2's coefficients
@@ -262,17 +301,29 @@ class BottleneckFn(Function):
             M3 = h2.numel() // h2.shape[-1]
             c3, u3 = C.bn_gram_coef(G, sv, ws[2], M3, bn3.weight.detach(), bn3.bias.detach(), bn3.running_mean,
                                     bn3.running_var, bn3.momentum, bn3.eps)
-            if block.down is not None:
+            if down_cat:
+                # hd = x W_d^T is linear in x as h3 is in a2: BN_d's coefficients (and running statistics) from
+                # (G_x, s_x, W_d) too, by the same routine, with u_d = W_d G_x for the backward as its by-product;
+                # then ONE streaming pass over [a2 | x] writes relu(BN3(a2 W3^T) + BN_d(x W_d^T)) -- no downsample
+                # conv, no bn_finalize for BN_d, hd neither written nor read
+                bnd_ = convs[3].bn
+                Gx, sx = C.bn_gram(x, None, C.bn_gram_pilot(x, False), False)
+                cd, ud = C.bn_gram_coef(Gx, sx, ws[3], M3, bnd_.weight.detach(), bnd_.bias.detach(), bnd_.running_mean,
+                                        bnd_.running_var, bnd_.momentum, bnd_.eps)
+                out, bits = C.conv1x1_apply_cat(src, ws[2], src_coef, c3, x, ws[3], cd)
+                if bnd_gram:
+                    bnd = (ud, sx)
+                else:
+                    # BN_d's backward through bn_bwd_partials(dz3, hd): hd for the backward alone (no statistics:
+                    # cd above is what the forward applied), the same output as with the Gram backward
+                    hd = C.conv_fwd(x, ws[3], *_conv_conf(dconv), False, None)[0]
+            elif block.down is not None:
                 out, bits = C.conv1x1_apply(src, ws[2], src_coef, c3, hd, cd)
             else:
                 out, bits = C.conv1x1_apply(src, ws[2], src_coef, c3, x, None)
             h3 = None
             gram = (u3, sv, M3)
-            dconv = block.down.conv if block.down is not None else None
-            if (_BND_GRAM and dconv is not None and tuple(dconv.kernel_size) == (1, 1) and tuple(dconv.padding) == (0, 0)
-                    and C.bnd_gram_ok(list(x.shape), dconv.out_channels, list(dconv.stride))
-                    and (tuple(dconv.stride) == (1, 1) or (_BND_GRAM_S2 and tuple(convs[0].conv.stride) == (1, 1) and
-                         C.pw_dgrad_strided_residual_ok(list(x.shape), convs[0].conv.out_channels)))):
+            if bnd_gram and not down_cat:
                 # BN_d's backward by Gram algebra: G_x, s_x of the plain block input (stride 2: of the pixels the
                 # downsample conv reads, x[:, ::2, ::2], by row addressing), centred on a pilot shift sampled from
                 # x itself (x has no producing BN here); only u_d = W_d G_x and s_x are kept
