@@ -12,6 +12,9 @@ values the kernel sees (the bf16-rounded tensors, widened), in the kernels' layo
     conv_emulate(...)                 the kernels' roundings in fp32 torch (no kernel)
     bn_case / bn_fwd_ref / bn_fwd_budgets / bn_bwd_ref / bn_emulate
     pool_case / maxpool_ref / gavg_ref
+    operand_on_load(h, coef, res, res_coef)   the operand of the kernels that apply BN + ReLU on load (bf16)
+    bnrelu_maxpool_ref / pool_gather_ref / maxpool_bn_bwd_ref / stem_wgrad_ref   the fused stem pool
+    pool_bn_case / conv_bn_case / bnin_fwd_case / bnin_bwd_case   cases of test_bn_fused_kernels_gpu.py
 
 Rounding constants (none is tuned to a kernel):
   U = 2^-8: one rounding to bf16.  bf16 keeps 8 significant bits, so the spacing in [2^e, 2^(e+1)) is 2^(e-7)
@@ -496,7 +499,8 @@ def bn_bwd_ref(dy, x, gamma, coef, mask=None, dgamma0=None, dbeta0=None):
     b_c = k1.abs() * b_s / M + mean.abs() * b_b + 4 * u32 * ((k1 * s / M).abs() + (b * mean).abs())
     rest = u32 * (k1 * dz).abs() + xd.abs() * b_b + b_c + 2 * u32 * ((k1 * dz).abs() + (b * xd).abs() + cc.abs())
     return dict(dz=dz, s=s, q=q, dx=dx, dgamma=dgamma + g0, dbeta=dbeta + b0, b_s=b_s + FLOOR, b_q=b_q + FLOOR,
-                b_dgamma=b_dgamma, b_dbeta=b_dbeta, b_dx=rest + U * (dx.abs() + rest) + FLOOR)
+                b_dgamma=b_dgamma, b_dbeta=b_dbeta, b_dx=rest + U * (dx.abs() + rest) + FLOOR,
+                k1=k1, b=b, c=cc, b_k1=u32 * k1.abs() + FLOOR, b_b=b_b + FLOOR, b_c=b_c + FLOOR)
 
 
 def bn_emulate(x, gamma, beta, rmean, rvar, dy, res=None, relu=False, eps=BN_EPS, mom=BN_MOM):
@@ -577,3 +581,460 @@ def gavg_ref(x):
     y = xd.mean(1)
     a = (HW + 1) * u32 * xd.abs().mean(1)
     return y, U * (y.abs() + a) + a + FLOOR
+
+
+# ==================================================== fused BN-boundary kernels
+# (test_bn_fused_kernels_gpu.py: the kernels that never store the tensor between a BatchNorm and its neighbour)
+def _f32(v):
+    """One round-to-nearest-even rounding of an fp64 tensor to fp32, widened again."""
+    return v.float().double()
+
+
+def operand_on_load(h, coef, res=None, res_coef=None):
+    """The conv / pool operand as the kernels form it, bf16: a = bf16(relu(fma(h, scale, shift) [+ r])).
+    h * scale + shift is exact in fp64 (a bf16 times an fp32 plus an fp32) and is rounded ONCE to fp32, the fma's
+    single rounding; a residual is one more fp32 addition.  With ``res_coef`` the residual is itself a BatchNorm
+    output, r = bf16(fma(res, scale_d, shift_d)): a second fma, rounded to bf16 first as bn_apply's two-BN form
+    and the on-load conv both do (the downsample branch is a bf16 tensor in the unfused network).  ReLU, then the
+    bf16 rounding.  On the dyadic grid nothing is rounded before that last step."""
+    c = coef.double()
+    v = _f32(h.double() * c[0] + c[1])
+    if res is not None:
+        r = res.double()
+        if res_coef is not None:
+            rc = res_coef.double()
+            r = _f32(r * rc[0] + rc[1]).to(BF).double()
+        v = _f32(v + r)
+    return (v.clamp(min=0) + 0.0).to(BF)
+
+
+def bn_bwd_apply_ref(dz, h, bcoef):
+    """dh = bf16(fma(a, dz, fma(b, h, c))) with bcoef = [a | b | c] per channel: two fp32 roundings (each of a
+    value exact in fp64), then the bf16 one."""
+    b = bcoef.double()
+    return _f32(b[0] * dz.double() + _f32(b[1] * h.double() + b[2])).to(BF)
+
+
+def _windows(a, k, s, p):
+    """a [N, H, W, C] fp64 -> its pooling windows [N, OH, OW, C, k k] in scan order (r, then q); padding = -inf."""
+    xp = F.pad(_nchw(a), (p, p, p, p), value=float("-inf"))
+    win = xp.unfold(2, k, s).unfold(3, k, s)  # [N, C, OH, OW, k, k]
+    N, C, OH, OW = win.shape[:4]
+    return win.reshape(N, C, OH, OW, k * k).permute(0, 2, 3, 1, 4)
+
+
+def bnrelu_maxpool_ref(h, coef, k, s, p, tie="first", relu_pad=False):
+    """maxpool(relu(BN(h))) from the definition: the operand of operand_on_load, a window maximum, and the argmax
+    byte r k + q of the FIRST maximal tap in scan order (the format maxpool_ref's kernels write).  Padding taps
+    never win.  Returns (y fp64, idx uint8, a bf16).  ``tie="last"`` / ``relu_pad`` (padding reads relu(shift)
+    instead of nothing) are the deliberately WRONG variants the CPU self-checks must tell apart."""
+    a = operand_on_load(h, coef)
+    win = _windows(a.double(), k, s, p)
+    if relu_pad:
+        pad_val = operand_on_load(torch.zeros(1, dtype=BF), coef).double()  # [C]
+        win = torch.where(torch.isinf(win), pad_val.view(1, 1, 1, -1, 1).expand_as(win), win)
+    y = win.amax(-1)
+    taps = torch.arange(k * k, dtype=torch.float64)
+    score = (win == y.unsqueeze(-1)).double() * ((k * k - taps) if tie == "first" else (taps + 1))
+    return y, score.argmax(-1).to(torch.uint8), a
+
+
+def last_valid_tap_idx(shape, k, s, p):
+    """Argmax bytes [N, OH, OW, C] in which every window names its LAST tap inside the image."""
+    win = _windows(torch.zeros(shape, dtype=torch.float64), k, s, p)
+    return ((~torch.isinf(win)).double() * (torch.arange(k * k, dtype=torch.float64) + 1)).argmax(-1).to(torch.uint8)
+
+
+def pool_gather_ref(dy, idx, H, W, k, s, p):
+    """fp64 max-pool backward THROUGH the argmax bytes: g[n, h, w, c] = sum of dy over the windows whose byte
+    names (h, w).  Returns (g, gabs) with gabs the same sum over |dy| (the rounding budget of the gather)."""
+    N, OH, OW, C = dy.shape
+    out = []
+    for d in (dy.double(), dy.double().abs()):
+        g = torch.zeros(N, H + 2 * p + k, W + 2 * p + k, C, dtype=torch.float64)
+        for t in range(k * k):
+            r, q = t // k, t % k
+            g[:, r:r + s * OH:s, q:q + s * OW:s] += d * (idx == t)
+        out.append(g[:, p:p + H, p:p + W].contiguous())
+    assert (idx < k * k).all()
+    return out
+
+
+def maxpool_bn_bwd_ref(dy, idx, h, gamma, coef, k, s, p, dgamma0=None, dbeta0=None, relu_ge=False):
+    """Backward of maxpool(relu(BN(h))): dy gathered through ``idx``, then bn_bwd_ref with the ReLU mask
+    h * scale + shift > 0 (the sign of the exact value is the sign of its fp32 rounding).  The gather adds at most
+    4 pooled gradients per pixel in fp32 (3 roundings, exact for integers): d = 3 u32 gabs per element, carried
+    through bn_bwd_ref's formulas -- ds = sum d, dq = sum d |x - mean|, db = k1 invstd^2 dq / M,
+    dc = k1 ds / M + |mean| db, and (1 + U)(|k1| d + |x| db + dc) on dx.
+    ``exact``: integer dy, invstd a power of two and 8 sum |dz (x - mean)| < 2^24 -- every term of both sums is a
+    multiple of 1/8 and every partial sum is exact in fp32, so dgamma and dbeta must equal the reference.
+    ``relu_ge``: the WRONG mask >= 0 (for the CPU self-checks)."""
+    N, H, W, C = h.shape
+    g, gabs = pool_gather_ref(dy, idx, H, W, k, s, p)
+    c = coef.double()
+    pre = h.double() * c[0] + c[1]
+    mask = (pre >= 0) if relu_ge else (pre > 0)
+    r = bn_bwd_ref(g.reshape(-1, C), h.reshape(-1, C), gamma, coef, mask.reshape(-1, C), dgamma0, dbeta0)
+    M = N * H * W
+    mean, invstd = c[2], c[3]
+    k1 = (gamma.double() * invstd).abs()
+    d = 3 * u32 * (gabs * mask).reshape(-1, C)
+    xc = (h.double().reshape(-1, C) - mean).abs()
+    ds, dq = d.sum(0), (d * xc).sum(0)
+    db = k1 * invstd ** 2 * dq / M
+    dc = k1 * ds / M + mean.abs() * db
+    r["b_dx"] = r["b_dx"] + (1 + U) * (k1 * d + h.double().reshape(-1, C).abs() * db + dc)
+    r["b_dgamma"] = r["b_dgamma"] + dq * invstd
+    r["b_dbeta"] = r["b_dbeta"] + ds
+    mag = (r["dz"] * (h.double().reshape(-1, C) - mean)).abs().sum(0).max().item()
+    r["exact"] = bool(torch.equal(dy.double(), dy.double().round()) and
+                      torch.equal(torch.log2(invstd), torch.log2(invstd).round()) and mag * 8 < 2 ** 24 and
+                      max(r["dgamma"].abs().max().item(), r["dbeta"].abs().max().item()) * 8 < 2 ** 24)
+    r["gathered"] = g
+    return r
+
+
+# ----- family 1 / 2 / 3: the stem's BN + ReLU + max-pool (3 / 2 / 1), forward and backward
+POOL_FWD = [(1, 2, 2, 64), (2, 8, 8, 64), (1, 6, 10, 64), (3, 7, 9, 64), (2, 9, 6, 64), (1, 5, 5, 16)]
+POOL_FWD_B = [(2, 8, 8, 64), (3, 7, 9, 64)]
+POOL_BWD = [sh for sh in POOL_FWD if sh[3] == 64] + [(4, 16, 16, 64)]  # (4, 16, 16): M / 512 = 2 partial blocks
+STEM_BWD = [(1, 2, 2), (2, 8, 8), (1, 6, 10), (5, 4, 20), (4, 16, 16)]   # (N, H, W), even H and W, C = 64
+
+
+@functools.lru_cache(maxsize=None)
+def pool_bn_case(shape, tier, seed=0):
+    """Operands of the fused stem pool at ``shape`` [N, H, W, C] (3 / 2 / 1), forward and backward.
+    Tier "A": h, coef from dyadic_bn (>= 5 % of every channel exactly at the ReLU threshold, scales of either
+    sign) with channel 0 given scale 0 and shift 1/2 (every tap of every window ties at 1/2) and channel 1
+    scale 1, shift 0 and h = -|h| (no positive pre-activation: every maximum is the ReLU's 0 and the first tap
+    inside the image must win); dy, the initial dgamma / dbeta and xs are small sparse integers.
+    Tier "B": randn h (x 2 + 0.3), coefficients from bn_fwd_ref over it (gamma[0] = 0: a zero scale;
+    gamma[2] < 0), randn dy / dgamma0 / dbeta0 / xs.
+    Also the reference forward (y, idx, a).  Cached: shared between tests, not to be modified."""
+    N, H, W, C = shape
+    gen = torch.Generator().manual_seed(5000 + seed + 7 * N + 11 * H + 13 * W)
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    gamma = 1 + 0.25 * torch.randn(C, generator=gen)
+    if tier == "A":
+        h, coef, pre = dyadic_bn(shape, 500 + seed + N + H + W, zero_frac=0.2)
+        # (off the threshold h is coarsened to multiples of 2, 9 values: the maximum of most windows is tied)
+        hd, coef = torch.where(pre == 0, h.double(), (h.double() / 2).round() * 2), coef.clone()
+        coef[0, 0], coef[1, 0] = 0.0, 0.5
+        hd[..., 1] = torch.where(pre[..., 1] == 0, torch.zeros_like(pre[..., 1]), -hd[..., 1].abs().clamp(min=0.125))
+        coef[0, 1], coef[1, 1] = 1.0, 0.0
+        hd[:, 0, 0, 1] = 0.0  # (window (0, 0)'s first tap inside the image sits at the threshold and wins it)
+        h = (hd + 0.0).to(BF)
+        assert (coef[0] < 0).any() and torch.equal(h.double(), hd + 0.0)
+        dy = _sparse_int((N, OH, OW, C), 0.7, gen, -3, 3)
+        dy[:, 0, 0, 1] = 1.0  # ... with a gradient on it: a mask decided with >= shows in dbeta at every shape
+        dy = dy.to(BF)
+        g0 = _sparse_int((C,), 0.8, gen, -9, 9).float()
+        b0 = _sparse_int((C,), 0.8, gen, -9, 9).float()
+        xs = _sparse_int((N, H, W, 16), 0.5, gen).to(BF)
+    else:
+        h = (torch.randn(shape, generator=gen) * 2 + 0.3).to(BF)
+        gamma[0] = 0.0
+        gamma[2] = -gamma[2].abs()
+        beta = 0.5 * torch.randn(C, generator=gen)
+        f = bn_fwd_ref(h.reshape(-1, C), gamma, beta, torch.zeros(C), torch.ones(C))
+        coef = torch.stack([f["scale"], f["shift"], f["mean"], f["invstd"]]).float()
+        dy = torch.randn(N, OH, OW, C, generator=gen).to(BF)
+        g0, b0 = torch.randn(C, generator=gen), torch.randn(C, generator=gen)
+        xs = torch.randn(N, H, W, 16, generator=gen).to(BF)
+    y, idx, a = bnrelu_maxpool_ref(h, coef, 3, 2, 1)
+    pre = h.double() * coef.double()[0] + coef.double()[1]
+    return dict(h=h, coef=coef, gamma=gamma, dy=dy, g0=g0, b0=b0, xs=xs, y=y, idx=idx, a=a, pre=pre)
+
+
+def check_pool_bn_case(shape, c):
+    """Tier A claims of pool_bn_case: >= 5 % of every channel at the threshold (the zero-scale channel is constant:
+    none or all), ties in most windows, channel 1 without a positive pre-activation, exact pre-activations."""
+    pre, C = c["pre"], shape[3]
+    at0 = (pre == 0).double().reshape(-1, C).mean(0)
+    if pre.numel() // C >= 100:
+        assert (at0[1:] >= 0.05).all(), at0.min().item()
+    assert (pre[..., 1] <= 0).all() and (pre[..., 1] < 0).any() and (pre[..., 0] == 0.5).all()
+    f32 = torch.addcmul(c["coef"][1].expand(shape), c["h"].float(), c["coef"][0].expand(shape))
+    assert torch.equal(f32.double(), pre) and torch.equal(pre * 32, (pre * 32).round()) and pre.abs().max() < 32
+    win = _windows(c["a"].double(), 3, 2, 1)
+    ties = ((win == win.amax(-1, keepdim=True)).sum(-1) > 1).double().mean().item()
+    assert ties > 0.3 or shape[1] * shape[2] <= 4, ties
+
+
+def stem_wgrad_ref(dh, xs):
+    """fp64 filter gradient [64, 4, 4, 16] of the s2d stem conv (4x4, pad 2-2-1-1) for dL/dY = dh [N, H, W, 64]
+    and input xs [N, H, W, 16], with conv_ref's fp32-accumulation budget b_dw."""
+    N, H, W, _ = xs.shape
+    g = G("stem_bwd", N, H, W, 16, 64, 4, pad=(2, 2, 1, 1))
+    r = conv_ref(xs, torch.zeros(64, 4, 4, 16), dh, g)
+    return r["dw"], r["b_dw"]
+
+
+# ----- family 4 / 5: BN + ReLU on a conv's operand (in_coef), row-walking 3x3 and streaming pointwise
+# row-walking kernel: 64 -> 64, 3x3 / 1 / 1, H >= 2, W <= 64.  (1, 1, 1) lies OUTSIDE it (H = 1: the plain conv
+# falls back to the implicit GEMM, which has no on-load transform, so conv_fwd raises with in_coef): it is pinned as
+# that error, and (1, 2, 1), the nearest shape inside, takes its place.  (16, 64, 3): the launch has
+# min(resident slots, N H / 16) blocks, so N H = 1024 is the smallest row count with 64 blocks, the threshold of
+# the weight grad's grouped partial reduce.
+ROW_BN = [(1, 2, 1), (2, 3, 5), (1, 9, 64), (3, 5, 33), (16, 64, 3)]
+ROW_BN_OUTSIDE = (1, 1, 1)
+# streaming pointwise kernel: C in {64, 128}, M % 32 == 0, Cout >= 2 C and a multiple of the forward's 256-column
+# block (pw_plan: N % (4 wn) == 0 with wn = 64 at both depths).  Cout = 64 lies outside for both channel counts; the
+# nearest inside is 256, already listed, so 512 (two column blocks) takes the vacant place.
+# M = N H W through (1, 4, 8), (2, 6, 8), (5, 13, 32).
+PW_BN_M = {32: (1, 4, 8), 96: (2, 6, 8), 2080: (5, 13, 32)}
+PW_BN = [(c, k, m) for c in (64, 128) for k in (256, 512) for m in PW_BN_M]
+
+
+def _dyadic_relu_shift(shape, seed):
+    """dyadic_bn with the sign of h and shift flipped on the channels whose shift is negative (all but every
+    eighth): relu(shift) != 0 on most channels, so a padding pixel that received the transform shows in y.  The
+    pre-activation flips sign with them; the elements at the threshold stay there."""
+    h, coef, pre = dyadic_bn(shape, seed, zero_frac=0.2)
+    C = shape[-1]
+    flip = (coef[1] < 0) & (torch.arange(C) % 8 != 7)
+    h = (torch.where(flip, -h.double(), h.double()) + 0.0).to(BF)
+    coef = coef.clone()
+    coef[1] = torch.where(flip, -coef[1], coef[1])
+    pre = torch.where(flip, -pre, pre) + 0.0
+    assert torch.equal(h.double() * coef.double()[0] + coef.double()[1], pre)
+    return h, coef, pre
+
+
+@functools.lru_cache(maxsize=None)
+def conv_bn_case(g, tier, seed=0):
+    """A conv of geometry ``g`` over a[.] = operand_on_load(h, coef): h, coef, w, dy, dw0 and the fp64 reference
+    over the reference operand (conv_ref; with the budgets in Tier B).
+    Tier "A": dyadic h / coef with relu(shift) != 0 on most channels, sparse integer w and dy.  a is a multiple
+    of 2^-5 below 2^5; the builder asserts that every sum of |products| stays below 2^24 2^-5, so fp32
+    accumulation is exact in any order: y must be bf16(ref) (one rounding), dw the reference itself.
+    ``stats_exact``: M max|y|^2 2^10 < 2^24 (y^2 is a multiple of 2^-10).
+    Tier "B": randn h, coefficients of a real bn_fwd_ref, randn w (/ sqrt(R S C)) and dy, all bf16."""
+    gen = torch.Generator().manual_seed(6000 + seed)
+    oh, ow = g.out_hw
+    if tier == "A":
+        h, coef, pre = _dyadic_relu_shift(g.xshape, 600 + seed)
+        dens = 0.5 if g.N * oh * ow <= 4096 else 0.25
+        w = _sparse_int((g.K, g.R, g.S, g.C), dens, gen)
+        for j in range(max(g.R * g.S, g.C, g.K)):  # every tap / channel residue under a nonzero weight
+            t = j % (g.R * g.S)
+            if w[j % g.K, t // g.S, t % g.S, j % g.C] == 0:
+                w[j % g.K, t // g.S, t % g.S, j % g.C] = (1, -1, 2, -2)[j % 4]
+        dy = _sparse_int((g.N, oh, ow, g.K), dens, gen)
+        dw0 = _sparse_int((g.K, g.R, g.S, g.C), 0.7, gen, -9, 9).float()
+    else:
+        h = torch.randn(g.xshape, generator=gen).to(BF)
+        gamma, beta = 1 + 0.25 * torch.randn(g.C, generator=gen), 0.5 * torch.randn(g.C, generator=gen)
+        f = bn_fwd_ref(h.reshape(-1, g.C), gamma, beta, torch.zeros(g.C), torch.ones(g.C))
+        coef = torch.stack([f["scale"], f["shift"], f["mean"], f["invstd"]]).float()
+        pre = h.double() * coef.double()[0] + coef.double()[1]
+        w = torch.randn(g.K, g.R, g.S, g.C, generator=gen) / (g.R * g.S * g.C) ** 0.5
+        dy = torch.randn(g.N, oh, ow, g.K, generator=gen)
+        dw0 = torch.randn(g.K, g.R, g.S, g.C, generator=gen)
+    w, dy = w.to(BF), dy.to(BF)
+    a = operand_on_load(h, coef)
+    c = conv_ref(a, w, dy, g, bounds=tier == "B")
+    c.update(h=h, coef=coef, w=w, dy=dy, dw0=dw0, a=a, pre=pre)
+    if tier == "A":
+        check_conv_bn_case(g, c)
+    return c
+
+
+def check_conv_bn_case(g, c):
+    """The exactness preconditions of a Tier A conv_bn_case ("reference not exact" when one fails)."""
+    a = c["a"].double()
+    assert torch.equal(a * 32, (a * 32).round()) and a.abs().max() < 32, (g.name, "operand off the 2^-5 grid")
+    for k in ("w", "dy"):
+        assert torch.equal(c[k].double(), c[k].double().round()) and c[k].double().abs().max() <= 2, (g.name, k)
+    m = conv_ref(a.abs(), c["w"].double().abs(), c["dy"].double().abs(), g, bounds=False)
+    for k in ("y", "dw"):
+        assert m[k].max().item() * 32 < 2 ** 24, (g.name, k, "reference not exact: a partial sum can leave fp32")
+    assert (c["dw"] / 2 + c["dw0"].double()).abs().max().item() * 64 < 2 ** 24, (g.name, "dw0 + dW / 2")
+    pre, C = c["pre"], g.C
+    if pre.numel() // C >= 100:
+        assert ((pre == 0).double().reshape(-1, C).mean(0) >= 0.05).all(), (g.name, "threshold hits")
+    sh = c["coef"][1]
+    assert (sh > 0).double().mean().item() >= 0.5, (g.name, "relu(shift) != 0 on most channels")
+    ymax = c["y"].abs().max().item()
+    c["stats_exact"] = g.M * ymax * ymax * 1024 < 2 ** 24
+
+
+def conv_bn_relu_pad_ref(c, g):
+    """The WRONG forward in which the padding receives the transform (reads relu(shift), not 0): for the CPU
+    self-checks."""
+    t, l, b, r = g.pad4
+    hp = F.pad(c["h"].double(), (0, 0, l, r, t, b))
+    ap = operand_on_load(hp.to(BF), c["coef"])
+    gp = G(g.name + "_padded", g.N, g.H + t + b, g.W + l + r, g.C, g.K, (g.R, g.S), g.stride, (0, 0), g.dil)
+    return conv_ref(ap, c["w"], torch.zeros(g.N, *gp.out_hw, g.K), gp, bounds=False)["y"]
+
+
+def row_bn_geom(n, h, w):
+    return G(f"rowbn_{n}_{h}_{w}", n, h, w, 64, 64, 3, pad=(1, 1))
+
+
+def pw_bn_geom(c, k, m):
+    return G(f"pwbn_{c}_{k}_m{m}", *PW_BN_M[m], c, k, 1)
+
+
+# ----- family 6 / 7: the BN applies on the A operand of the LDS-DMA 1x1 conv
+BNIN_M = {1: (1, 1, 1), 127: (1, 1, 127), 128: (2, 8, 8), 129: (1, 3, 43), 243: (3, 9, 9)}
+BNIN_FWD = [(m, c, k) for m in BNIN_M for c in (32, 64, 256) for k in (8, 64, 136)]   # x [M, C] -> y [M, K]
+BNIN_BWD = [(m, k, c) for m in BNIN_M for k in (32, 64, 256) for c in (8, 64, 136)]   # dz [M, K] -> dx [M, C]
+
+
+@functools.lru_cache(maxsize=None)
+def bnin_fwd_case(m, C, K, tier, down, seed=0):
+    """conv1x1_bnin_fwd operands at M = m rows: h, res, coef, res_coef (``down``: the residual is a BatchNorm
+    output itself), w, and the reference operand x, its ReLU bits, and the geometry of the 1x1 conv over it.
+    Tier "A": everything on the dyadic grid (h * scale + shift + r is a multiple of 2^-5 below 2^6: exact in
+    fp32, one bf16 rounding), the residual branch 0 wherever the main branch is at its threshold, so >= 5 % of
+    every channel has a pre-activation of exactly 0; sparse integer w.  Tier "B": randn, real coefficients."""
+    shape = (*BNIN_M[m], C)
+    g = G(f"bnin_f_{m}_{C}_{K}", *shape, K, 1)
+    gen = torch.Generator().manual_seed(7000 + seed + m + 3 * C + 5 * K + down)
+    if tier == "A":
+        h, coef, pre = dyadic_bn(shape, 700 + seed + m + C, zero_frac=0.2)
+        if down:
+            res, res_coef, pre2 = dyadic_bn(shape, 750 + seed + m + C)
+            h02 = (-res_coef.double()[1] / res_coef.double()[0])  # the branch's own threshold, on the grid
+            res = (torch.where(pre == 0, h02.expand(shape), res.double()) + 0.0).to(BF)
+        else:
+            r = torch.randint(-64, 65, shape, generator=gen).double() / 8
+            res, res_coef = torch.where(pre == 0, torch.zeros_like(r), r).to(BF), None
+        w = _sparse_int((K, 1, 1, C), 0.4, gen)
+        for j in range(max(C, K)):
+            if w[j % K, 0, 0, j % C] == 0:
+                w[j % K, 0, 0, j % C] = (1, -1, 2, -2)[j % 4]
+    else:
+        h = torch.randn(shape, generator=gen).to(BF)
+        res = torch.randn(shape, generator=gen).to(BF)
+
+        def real_coef(t):
+            gamma, beta = 1 + 0.25 * torch.randn(C, generator=gen), 0.5 * torch.randn(C, generator=gen)
+            f = bn_fwd_ref(t.reshape(-1, C), gamma, beta, torch.zeros(C), torch.ones(C))
+            return torch.stack([f["scale"], f["shift"], f["mean"], f["invstd"]]).float()
+        coef = real_coef(h)
+        res_coef = real_coef(res) if down else None
+        w = torch.randn(K, 1, 1, C, generator=gen) / C ** 0.5
+    w = w.to(BF)
+    x = operand_on_load(h, coef, res, res_coef)
+    c = dict(h=h, res=res, coef=coef, res_coef=res_coef, w=w, x=x, bits=pack_bits(x > 0), g=g)
+    if tier == "A":
+        xd = x.double()
+        assert torch.equal(xd * 32, (xd * 32).round()) and xd.max() < 64, (g.name, "operand off the 2^-5 grid")
+        if xd.numel() // C >= 100:
+            t = h.double() * coef.double()[0] + coef.double()[1]
+            t = t + (res.double() if not down else (res.double() * res_coef.double()[0] + res_coef.double()[1]))
+            assert ((t == 0).double().reshape(-1, C).mean(0) >= 0.05).all(), (g.name, "threshold hits")
+        mag = conv_ref(xd, w.double().abs(), torch.zeros(*shape[:3], K), g, bounds=False)["y"].max().item()
+        assert mag * 32 < 2 ** 24, (g.name, "reference not exact")
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def bnin_bwd_case(m, K, C, tier, seed=0):
+    """conv1x1_bnin_dgrad operands: dz, h3 [M, K], bcoef [3][K], w [K, 1, 1, C], and (bn_x, bn_coef) [M, C] of the
+    BN + ReLU that produced the conv's input; with the reference dh = bn_bwd_apply_ref.
+    Tier "A": integer dz in [-2, 2], h3 on the 1/8 grid, a a power of two in [1/2, 2] of either sign, b a multiple
+    of 1/8 in [-1, 1], c one in [-2, 2]: a dz + b h3 + c is a multiple of 2^-6 below 2^4, exact in fp32 at every
+    step; sparse integer w; (bn_x, bn_coef) from dyadic_bn.  Tier "B": randn, bcoef from a real bn_bwd_ref."""
+    shape = (*BNIN_M[m], K)
+    xshape = (*BNIN_M[m], C)
+    g = G(f"bnin_b_{m}_{K}_{C}", *xshape, K, 1)
+    gen = torch.Generator().manual_seed(8000 + seed + m + 3 * C + 5 * K)
+    if tier == "A":
+        dz = _sparse_int(shape, 0.6, gen).to(BF)
+        h3 = (torch.randint(-64, 65, shape, generator=gen).double() / 8).to(BF)
+        a = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (K,), generator=gen)]
+        a = a * (torch.randint(0, 2, (K,), generator=gen) * 2 - 1)
+        bcoef = torch.stack([a, torch.randint(-8, 9, (K,), generator=gen) / 8,
+                             torch.randint(-16, 17, (K,), generator=gen) / 8]).float()
+        w = _sparse_int((K, 1, 1, C), 0.3, gen)
+        for j in range(max(C, K)):
+            if w[j % K, 0, 0, j % C] == 0:
+                w[j % K, 0, 0, j % C] = (1, -1, 2, -2)[j % 4]
+        bn_x, bn_coef, pre = dyadic_bn(xshape, 800 + seed + m + C, zero_frac=0.2)
+        bc = bn_coef.double()
+        bn_x = bn_x.clone()
+        bn_x[0, 0, 0] = (-bc[1] / bc[0]).to(BF)  # (row 0 wholly at the threshold: also M = 1 has hits)
+    else:
+        dz = torch.randn(shape, generator=gen).to(BF)
+        h3 = torch.randn(shape, generator=gen).to(BF)
+        gamma = 1 + 0.25 * torch.randn(K, generator=gen)
+        f = bn_fwd_ref(h3.reshape(-1, K), gamma, torch.zeros(K), torch.zeros(K), torch.ones(K))
+        c3 = torch.stack([f["scale"], f["shift"], f["mean"], f["invstd"]]).float()
+        bw = bn_bwd_ref(dz.reshape(-1, K), h3.reshape(-1, K), gamma, c3)
+        bcoef = torch.stack([bw["k1"], bw["b"], bw["c"]]).float()
+        w = torch.randn(K, 1, 1, C, generator=gen) / K ** 0.5
+        bn_x = torch.randn(xshape, generator=gen).to(BF)
+        g2, b2 = 1 + 0.25 * torch.randn(C, generator=gen), 0.5 * torch.randn(C, generator=gen)
+        f2 = bn_fwd_ref(bn_x.reshape(-1, C), g2, b2, torch.zeros(C), torch.ones(C))
+        bn_coef = torch.stack([f2["scale"], f2["shift"], f2["mean"], f2["invstd"]]).float()
+    w = w.to(BF)
+    dh = bn_bwd_apply_ref(dz, h3, bcoef)
+    c = dict(dz=dz, h3=h3, bcoef=bcoef, w=w, bn_x=bn_x, bn_coef=bn_coef, dh=dh, g=g)
+    if tier == "A":
+        b = bcoef.double()
+        exact = b[0] * dz.double() + b[1] * h3.double() + b[2]
+        inner = b[1] * h3.double() + b[2]
+        assert torch.equal(exact.float().double(), exact) and torch.equal(inner.float().double(), inner)
+        assert torch.equal(exact * 64, (exact * 64).round()) and exact.abs().max() < 16, (g.name, "dh off the 2^-6 grid")
+        mag = conv_ref(torch.zeros(xshape), w.double().abs(), dh.double().abs(), g, bounds=False)["dx"].max().item()
+        assert mag * 64 < 2 ** 24, (g.name, "reference not exact")
+    return c
+
+
+def partials_ref(dz, x, coef):
+    """fp64 [sum dz, sum dz (x - mean)] per channel and the fp32 budgets of bn_bwd_ref (b_s = M u32 sum |dz|,
+    b_q = (M + 2) u32 sum |dz (x - mean)|); ``exact``: every term a multiple of 2^-9 (dz of 2^-6, x - mean of
+    2^-3) and 2^9 sum |terms| < 2^24, so any fp32 summation order gives the reference itself."""
+    C = dz.shape[-1]
+    d, xc = dz.double().reshape(-1, C), x.double().reshape(-1, C) - coef.double()[2]
+    M = d.shape[0]
+    ref = torch.stack([d.sum(0), (d * xc).sum(0)])
+    mag = torch.stack([d.abs().sum(0), (d * xc).abs().sum(0)])
+    bound = torch.stack([M * u32 * mag[0], (M + 2) * u32 * mag[1]]) + FLOOR
+    on_grid = torch.equal(d * 64, (d * 64).round()) and torch.equal(xc * 8, (xc * 8).round())
+    return ref, bound, bool(on_grid and mag.max().item() * 512 < 2 ** 24)
+
+
+# ----- emulations (fp32 torch on the CPU, no kernel) of the arithmetic the budgets above are counted from
+def conv_bn_emulate(c, g, alpha=0.5):
+    """Operand on load, bf16 round, fp32 product, bf16 round (dw: fp32, dw0 + alpha dW)."""
+    y, _, dw = conv_emulate(c["a"], c["w"], c["dy"], g)
+    return y, c["dw0"] + alpha * dw
+
+
+def pool_bn_bwd_emulate(c, idx, H, W):
+    """maxpool_bn_bwd in fp32: gather (fp32 adds), mask, fp32 sums, bn.hip's finalize, dh = bf16(a dz + (b h + c)).
+    Returns (dh, dgamma, dbeta) accumulated onto g0 / b0."""
+    C = c["h"].shape[-1]
+    g, _ = pool_gather_ref(c["dy"], idx, H, W, 3, 2, 1)
+    dz = (g.float() * (c["pre"] > 0)).reshape(-1, C)
+    hf, coef = c["h"].float().reshape(-1, C), c["coef"]
+    M = hf.shape[0]
+    s, q = dz.sum(0).double(), (dz * (hf - coef[2])).sum(0).double()
+    dgamma, dbeta = c["g0"] + (q * coef[3].double()).float(), c["b0"] + s.float()
+    k1, b, cc = bn_bwd_finalize_emulate(s, q, M, c["gamma"], coef)
+    return (k1 * dz + (b * hf + cc)).to(BF).reshape(c["h"].shape), dgamma, dbeta
+
+
+def bn_bwd_finalize_emulate(s, q, M, gamma, coef):
+    """bn.hip's bn_bwd_finalize in fp32 from the (double) sums: a = k1 = gamma invstd, b = -k1 invstd^2 q / M,
+    c = -k1 s / M - b mean, with 1 / M formed once in fp32."""
+    k1 = gamma.float() * coef[3]
+    invM = torch.tensor(1.0) / torch.tensor(float(M))
+    b = -k1 * coef[3] * coef[3] * q.float() * invM
+    return k1, b, -k1 * s.float() * invM - b * coef[2]
+
+
+def split_partials(dz, x, coef):
+    """BN-backward partials [2][C][2] as a producer's epilogue would hand them over: the fp64 sums of the first
+    ceil(M / 2) rows and of the rest, each rounded once to fp32 (u32 |sum| per column: inside b_s and b_q)."""
+    d = dz.double()
+    xc = x.double() - coef.double()[2]
+    M = d.shape[0]
+    k = (M + 1) // 2
+    cols = [torch.stack([d[a:b].sum(0), (d[a:b] * xc[a:b]).sum(0)]) for a, b in ((0, k), (k, M))]
+    return torch.stack(cols, -1).float().contiguous()

@@ -255,3 +255,189 @@ def test_gavg_emulation_within_budget(H, W, C):
     assert _ratio(e, y, b) <= 1.0
     dxr = dy.double() / (H * W)
     assert _ratio((dy.float() * (1.0 / (H * W))).to(BF), dxr, (R.U + 3 * R.u32) * dxr.abs() + R.FLOOR) <= 1.0
+
+
+# ------------------------------------------- fused BN-boundary kernels (test_bn_fused_kernels_gpu.py)
+def _rows(t, C):
+    return t.reshape(-1, C)
+
+
+def test_fused_case_lists_cover_the_issue():
+    assert set(R.POOL_FWD) == {(1, 2, 2, 64), (2, 8, 8, 64), (1, 6, 10, 64), (3, 7, 9, 64), (2, 9, 6, 64), (1, 5, 5, 16)}
+    assert set(R.POOL_FWD_B) == {(2, 8, 8, 64), (3, 7, 9, 64)}
+    assert set(R.POOL_BWD) == {s for s in R.POOL_FWD if s[3] == 64} | {(4, 16, 16, 64)} and 4 * 16 * 16 // 512 == 2
+    assert set(R.STEM_BWD) == {(1, 2, 2), (2, 8, 8), (1, 6, 10), (5, 4, 20), (4, 16, 16)}
+    # (1, 1, 1) is outside the row-walking kernel (H >= 2): pinned as an error, (1, 2, 1) in its place
+    assert {(2, 3, 5), (1, 9, 64), (3, 5, 33), (1, 2, 1)} <= set(R.ROW_BN) and R.ROW_BN_OUTSIDE == (1, 1, 1)
+    assert any(n * h // 16 >= 64 for n, h, _ in R.ROW_BN) and min(n * h for n, h, _ in R.ROW_BN if n * h // 16 >= 64) == 1024
+    assert {m for _, _, m in R.PW_BN} == {32, 96, 2080} and {c for c, _, _ in R.PW_BN} == {64, 128}
+    assert all(k >= 2 * c and k % 256 == 0 for c, k, _ in R.PW_BN) and 256 in {k for _, k, _ in R.PW_BN}
+    assert all(n * h * w == m for m, (n, h, w) in list(R.PW_BN_M.items()) + list(R.BNIN_M.items()))
+    assert set(R.BNIN_M) == {1, 127, 128, 129, 243}
+    assert {(c, k) for _, c, k in R.BNIN_FWD} == {(c, k) for c in (32, 64, 256) for k in (8, 64, 136)}
+    assert {(k, c) for _, k, c in R.BNIN_BWD} == {(k, c) for k in (32, 64, 256) for c in (8, 64, 136)}
+
+
+def test_operand_on_load():
+    """Tier A: nothing rounds before the bf16 store (plain fp32 arithmetic gives the same bits).  randn: one fp32
+    rounding of the exact h * scale + shift, inside bn_apply_ref's budget, and NOT always the single-rounding fp64
+    value (the reason the reference exists)."""
+    h, coef, pre = R.dyadic_bn((2, 5, 9, 32), 3)
+    a = R.operand_on_load(h, coef)
+    assert torch.equal(a, (h.float() * coef[0] + coef[1]).clamp(min=0).to(BF)) and torch.equal(a.double(), pre.clamp(min=0).to(BF).double())
+    c = R.bnin_fwd_case(243, 64, 8, "B", True)
+    for res, rc in ((None, None), (c["res"], None), (c["res"], c["res_coef"])):
+        a = R.operand_on_load(c["h"], c["coef"], res, rc)
+        r = res if rc is None else R.operand_on_load(res, rc).double() * 0 + R._f32(res.double() * rc.double()[0] + rc.double()[1]).to(BF).double()
+        y, b = R.bn_apply_ref(c["h"], c["coef"], r, True)
+        assert _ratio(a, y, b) <= 1.0
+    v = (c["h"].double() * c["coef"].double()[0] + c["coef"].double()[1])
+    assert (v.float() != v).any()
+
+
+@pytest.mark.parametrize("shape", sorted(set(R.POOL_FWD + R.POOL_BWD + [(*s, 64) for s in R.STEM_BWD])))
+def test_pool_bn_case_tier_a(shape):
+    """Tier A claims of the fused stem pool cases; the reference forward / gather against torch's max_pool2d and
+    its autograd over the reference operand; and the four deliberately wrong references are told apart."""
+    N, H, W, C = shape
+    c = R.pool_bn_case(shape, "A")
+    R.check_pool_bn_case(shape, c)
+    y, dx = R.maxpool_ref(c["a"], c["dy"], 3, 2, 1)
+    g, gabs = R.pool_gather_ref(c["dy"], c["idx"], H, W, 3, 2, 1)
+    assert torch.equal(y, c["y"]) and torch.equal(dx, g) and (gabs >= g.abs()).all()
+    assert (c["y"][..., 1] == 0).all() and (c["y"][..., 0] == 0.5).all()
+    # first tap inside the image on the constant channels: tap 4 at window (0, 0), 3 on the first row, 1 on the first column
+    for ch in (0, 1):
+        assert c["idx"][0, 0, 0, ch] == 4
+        if c["idx"].shape[1] > 1 and c["idx"].shape[2] > 1:
+            assert c["idx"][0, 0, 1, ch] == 3 and c["idx"][0, 1, 0, ch] == 1 and c["idx"][0, 1, 1, ch] == 0
+    # wrong: last-tap tie break; relu(shift) in the padding
+    _, idx_last, _ = R.bnrelu_maxpool_ref(c["h"], c["coef"], 3, 2, 1, tie="last")
+    assert not torch.equal(idx_last, c["idx"])
+    y_pad, idx_pad, _ = R.bnrelu_maxpool_ref(c["h"], c["coef"], 3, 2, 1, relu_pad=True)
+    assert not torch.equal(idx_pad, c["idx"]) or not torch.equal(y_pad, c["y"])
+    if C != 64:
+        return
+    args = (c["h"], c["gamma"], c["coef"], 3, 2, 1, c["g0"], c["b0"])
+    r = R.maxpool_bn_bwd_ref(c["dy"], c["idx"], *args)
+    assert r["exact"], "reference not exact"
+    # wrong: ReLU with >=; the gather recomputing the max instead of following idx
+    ge = R.maxpool_bn_bwd_ref(c["dy"], c["idx"], *args, relu_ge=True)
+    assert not torch.equal(ge["dbeta"], r["dbeta"]) and ((ge["dx"] - r["dx"]).abs() > r["b_dx"]).any()
+    last = R.last_valid_tap_idx(shape, 3, 2, 1)
+    assert (last >= c["idx"]).all() and not torch.equal(last, c["idx"])
+    rl = R.maxpool_bn_bwd_ref(c["dy"], last, *args)
+    assert ((rl["dx"] - r["dx"]).abs() > r["b_dx"]).any() and not torch.equal(rl["gathered"], r["gathered"])
+    # emulation: exact dgamma / dbeta, dh inside its budget
+    dh, dg, db = R.pool_bn_bwd_emulate(c, c["idx"], H, W)
+    assert torch.equal(dg.double(), r["dgamma"]) and torch.equal(db.double(), r["dbeta"])
+    assert _ratio(_rows(dh, C), r["dx"], r["b_dx"]) <= 1.0
+    dh, dg, db = R.pool_bn_bwd_emulate(c, last, H, W)
+    assert torch.equal(dg.double(), rl["dgamma"]) and _ratio(_rows(dh, C), rl["dx"], rl["b_dx"]) <= 1.0
+
+
+@pytest.mark.parametrize("shape", R.POOL_FWD_B + [(4, 16, 16, 64)])
+def test_pool_bn_bwd_emulation_within_budgets(shape):
+    """randn: fp32 gather, sums, finalize and apply stay inside maxpool_bn_bwd_ref's budgets; the stem weight grad
+    from the rounded dh inside stem_wgrad_ref's."""
+    N, H, W, C = shape
+    c = R.pool_bn_case(shape, "B")
+    r = R.maxpool_bn_bwd_ref(c["dy"], c["idx"], c["h"], c["gamma"], c["coef"], 3, 2, 1, c["g0"], c["b0"])
+    dh, dg, db = R.pool_bn_bwd_emulate(c, c["idx"], H, W)
+    rs = {"dh": _ratio(_rows(dh, C), r["dx"], r["b_dx"]), "dgamma": _ratio(dg, r["dgamma"], r["b_dgamma"]),
+          "dbeta": _ratio(db, r["dbeta"], r["b_dbeta"])}
+    if H % 2 == 0 and W % 2 == 0:
+        dw, b_dw = R.stem_wgrad_ref(dh, c["xs"])
+        dw0 = torch.randn(64, 4, 4, 16, generator=torch.Generator().manual_seed(1))
+        xn = F.pad(c["xs"].float().permute(0, 3, 1, 2), (2, 1, 2, 1))
+        e = torch.nn.grad.conv2d_weight(xn, [64, 16, 4, 4], dh.float().permute(0, 3, 1, 2)).permute(0, 2, 3, 1) + dw0
+        rs["dw"] = _ratio(e, dw + dw0.double(), b_dw + R.u32 * (dw + dw0.double()).abs())
+        # a dropped border tap is far outside
+        bad = dh.clone()
+        bad[:, 0, 0] = 0
+        dwb, _ = R.stem_wgrad_ref(bad, c["xs"])
+        assert _ratio(dwb.float(), dw, b_dw) > 1.0
+    print(shape, {k: round(v, 3) for k, v in rs.items()})
+    assert all(v <= 1.0 for v in rs.values()), rs
+
+
+CONV_BN_GEOMS = [R.row_bn_geom(*s) for s in R.ROW_BN] + [R.pw_bn_geom(*s) for s in R.PW_BN]
+
+
+@pytest.mark.parametrize("g", CONV_BN_GEOMS, ids=[g.name for g in CONV_BN_GEOMS])
+def test_conv_bn_cases(g):
+    """Tier A: the exactness preconditions hold (asserted by the builder), the fp32 emulation reproduces the
+    reference bit for bit, and a padding that received the transform is told apart (3x3).  Tier B: the emulation
+    stays inside conv_ref's budgets over the reference operand."""
+    c = R.conv_bn_case(g, "A")
+    R.check_conv_bn_case(g, c)
+    y, dw = R.conv_bn_emulate(c, g)
+    assert torch.equal(y, c["y"].to(BF)) and torch.equal(dw.double(), c["dw0"].double() + c["dw"] / 2)
+    if g.R == 3:
+        assert not torch.equal(R.conv_bn_relu_pad_ref(c, g).to(BF), c["y"].to(BF))
+    c = R.conv_bn_case(g, "B")
+    y, dw = R.conv_bn_emulate(c, g)
+    dwref = c["dw0"].double() + c["dw"] / 2
+    rs = {"y": _ratio(y, c["y"], c["b_y"]), "dw": _ratio(dw, dwref, c["b_dw"] / 2 + R.u32 * dwref.abs())}
+    assert all(v <= 1.0 for v in rs.values()), rs
+
+
+@pytest.mark.parametrize("m,C,K", R.BNIN_FWD)
+def test_bnin_fwd_cases(m, C, K):
+    for down in (False, True):
+        c = R.bnin_fwd_case(m, C, K, "A", down)
+        g = c["g"]
+        ref = R.conv_ref(c["x"], c["w"], torch.zeros(*g.xshape[:3], K), g, bounds=False)
+        y, _, _ = R.conv_emulate(c["x"], c["w"], torch.zeros(*g.xshape[:3], K), g)
+        assert torch.equal(y, ref["y"].to(BF))
+        assert not torch.equal(R.pack_bits(c["x"] >= 0), c["bits"])  # wrong: ReLU bits decided with >=
+        c = R.bnin_fwd_case(m, C, K, "B", down)
+        ref = R.conv_ref(c["x"], c["w"], torch.zeros(*g.xshape[:3], K), g)
+        y, _, _ = R.conv_emulate(c["x"], c["w"], torch.zeros(*g.xshape[:3], K), g)
+        assert _ratio(y, ref["y"], ref["b_y"]) <= 1.0
+
+
+@pytest.mark.parametrize("m,K,C", R.BNIN_BWD)
+def test_bnin_bwd_cases(m, K, C):
+    c = R.bnin_bwd_case(m, K, C, "A")
+    g = c["g"]
+    b = c["bcoef"]
+    assert torch.equal((b[0] * c["dz"].float() + (b[1] * c["h3"].float() + b[2])).to(BF), c["dh"])
+    ref = R.conv_ref(torch.zeros(g.xshape), c["w"], c["dh"], g, bounds=False)
+    _, dx, _ = R.conv_emulate(torch.zeros(g.xshape).to(BF), c["w"], c["dh"], g)
+    assert torch.equal(dx, ref["dx"].to(BF))
+    dz, pref = R.dgrad_bn_ref(dx.double(), c["bn_x"], c["bn_coef"])
+    cd = c["bn_coef"].double()
+    _, wrong = R.dgrad_bn_ref(dx.double(), c["bn_x"], c["bn_coef"], (c["bn_x"].double() * cd[0] + cd[1]) >= 0)
+    assert not torch.equal(wrong, pref), "a mask decided with >= would pass"
+    p2, bound, exact = R.partials_ref(dz, c["bn_x"], c["bn_coef"])
+    assert torch.equal(p2, pref)
+    e = torch.stack([dz.float().reshape(-1, C).sum(0), (dz.float() * (c["bn_x"].float() - c["bn_coef"][2])).reshape(-1, C).sum(0)])
+    assert _ratio(e, pref, bound) <= 1.0 and (not exact or torch.equal(e.double(), pref))
+    c = R.bnin_bwd_case(m, K, C, "B")
+    b = c["bcoef"]
+    e = (b[0] * c["dz"].float() + (b[1] * c["h3"].float() + b[2])).to(BF)  # (no fma: up to one more fp32 rounding)
+    d = c["dh"].double()
+    mag = (b[0].double() * c["dz"].double()).abs() + (b[1].double() * c["h3"].double()).abs() + b[2].double().abs()
+    # (two bf16 roundings of pre-rounding values 3 u32 mag apart: at most the two half-spacings plus that distance;
+    # few elements differ at all -- the GPU test compares the kernel's fma chain bit for bit)
+    assert _ratio(e, d, 2 * R.U * d.abs() + (1 + R.U) * 3 * R.u32 * mag + R.FLOOR) <= 1.0
+    assert m == 1 or (e != c["dh"]).double().mean().item() < 0.01  # (M = 1: dh is pure cancellation, ~0)
+    ref = R.conv_ref(torch.zeros(g.xshape), c["w"], c["dh"], g)
+    _, dx, _ = R.conv_emulate(torch.zeros(g.xshape).to(BF), c["w"], c["dh"], g)
+    assert _ratio(dx, ref["dx"], ref["b_dx"]) <= 1.0
+
+
+@pytest.mark.parametrize("M,C", BN_SHAPES)
+def test_bn_bwd_coef_emulation_within_budgets(M, C):
+    """bn_bwd_finalize's fp32 coefficient arithmetic from partials rounded to fp32 (as the GPU test feeds them):
+    a, b, c inside b_k1, b_b, b_c of bn_bwd_ref."""
+    c = R.bn_case(M, C, seed=M + C)
+    f = R.bn_fwd_ref(c["x"], c["gamma"], c["beta"], c["rmean"], c["rvar"])
+    coef = torch.stack([f["scale"], f["shift"], f["mean"], f["invstd"]]).float()
+    bw = R.bn_bwd_ref(c["dy"], c["x"], c["gamma"], coef)
+    part = R.split_partials(bw["dz"], c["x"], coef)
+    k1, b, cc = R.bn_bwd_finalize_emulate(part[0].double().sum(-1), part[1].double().sum(-1), M, c["gamma"], coef)
+    rs = {"a": _ratio(k1, bw["k1"], bw["b_k1"]), "b": _ratio(b, bw["b"], bw["b_b"]), "c": _ratio(cc, bw["c"], bw["b_c"])}
+    print(M, C, {k: round(v, 3) for k, v in rs.items()})
+    assert all(v <= 1.0 for v in rs.values()), rs
