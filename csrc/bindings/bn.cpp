@@ -165,6 +165,69 @@ std::vector<Tensor> conv1x1_apply(const Tensor& x, const Tensor& w, const c10::o
   return {y, bits};
 }
 
+// The envelope of conv1x1_apply_next: a conv3 over h2shape [N, H, W, 64] -> cout3 == 256 on the streaming kernel whose
+// pass also forms the next block's 1x1 stride-1 conv1 (256 -> c1_next in {64, 128}).  False while a CU budget is in
+// force with the dynamic schedule on (no dynamic variant is built): the caller then makes the two separate calls.
+bool c1_fuse_ok(const std::vector<int64_t>& h2shape, int64_t cout3, int64_t c1_next) {
+  if (h2shape.size() != 4 || !pw_stream_on()) return false;
+  const int64_t M = h2shape[0] * h2shape[1] * h2shape[2];
+  return cout3 == 256 && h2shape[3] == 64 && (c1_next == 64 || c1_next == 128) &&
+         dpe_pw_next_rowgroups(M, cout3, h2shape[3], c1_next) > 0;
+}
+
+// conv1x1_apply with the next block's conv1 in the same streaming pass: (y, bits) exactly as conv1x1_apply(x, w,
+// in_coef, out_coef, residual, None) and h1 = y W_next^T [.., c1_next] (from the stored bf16 y, fp32 sums, rounded
+// once) with the BatchNorm-forward partials st [2][c1_next][row groups] of the stored h1 (bn_coef's input, as
+// conv_fwd's).  A BN'd residual (res_coef) is outside the envelope.  Returns (y, bits, h1, st); ``outs``: these four
+// given by the caller (exact shapes and types, contiguous; row groups from a first call) instead of allocated here.
+std::vector<Tensor> conv1x1_apply_next(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& in_coef,
+                                       const Tensor& out_coef, const Tensor& residual, const c10::optional<Tensor>& res_coef,
+                                       const Tensor& w_next, const c10::optional<std::vector<Tensor>>& outs) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(w); CHECK_CONTIG(w); CHECK_F32(out_coef); CHECK_CONTIG(out_coef);
+  CHECK_GPU(residual); CHECK_BF16(residual); CHECK_CONTIG(residual); CHECK_GPU(w_next); CHECK_BF16(w_next); CHECK_CONTIG(w_next);
+  TORCH_CHECK(!has(res_coef), "conv1x1_apply_next: a BN'd residual is outside the envelope");
+  TORCH_CHECK(x.dim() == 4, "conv1x1_apply_next: x must be [N, H, W, K]");
+  const int64_t K = x.size(-1), M = x.numel() / K, N = w.size(0), C1 = w_next.size(0);
+  TORCH_CHECK(w.numel() == N * K && out_coef.numel() == 4 * N && w_next.numel() == C1 * N, "conv1x1_apply_next: shapes");
+  if (has(in_coef)) {
+    CHECK_F32((*in_coef)); CHECK_CONTIG((*in_coef));
+    TORCH_CHECK(in_coef->numel() >= 2 * K, "conv1x1_apply_next: in_coef must be the BN's [4][K] coefficients");
+  }
+  auto ysz = x.sizes().vec();
+  ysz.back() = N;
+  TORCH_CHECK(residual.sizes().vec() == ysz, "conv1x1_apply_next: residual must have the output's shape");
+  TORCH_CHECK(c1_fuse_ok(x.sizes().vec(), N, C1), "conv1x1_apply_next: outside the envelope (c1_fuse_ok)");
+  const int rg = dpe_pw_next_rowgroups(M, N, K, C1);
+  Tensor y = at::empty(ysz, x.options());
+  auto bsz = ysz;
+  bsz.back() = N / 8;
+  Tensor bits = at::empty(bsz, x.options().dtype(at::kByte));
+  auto hsz = ysz;
+  hsz.back() = C1;
+  Tensor h1 = at::empty(hsz, x.options());
+  Tensor st = at::empty({2, C1, rg}, x.options().dtype(at::kFloat));
+  if (outs.has_value()) {
+    TORCH_CHECK(outs->size() == 4, "conv1x1_apply_next: outs must be (y, bits, h1, st)");
+    const Tensor* mine[4] = {&y, &bits, &h1, &st};
+    for (int i = 0; i < 4; ++i) {
+      const Tensor& o = (*outs)[i];
+      TORCH_CHECK(o.is_cuda() && o.is_contiguous() && o.sizes() == mine[i]->sizes() && o.scalar_type() == mine[i]->scalar_type(),
+                  "conv1x1_apply_next: outs[", i, "] has the wrong shape, type or layout");
+    }
+    y = (*outs)[0]; bits = (*outs)[1]; h1 = (*outs)[2]; st = (*outs)[3];
+  }
+  dpe::PwArgs pa{};
+  pa.x = bp(x); pa.w = bp(w); pa.y = bpm(y);
+  pa.in_coef = fpo(in_coef);
+  pa.out_coef = fp(out_coef);
+  pa.residual = bp(residual);
+  pa.out_bits = (uint8_t*)bits.data_ptr();
+  pa.w_next = bp(w_next); pa.y_next = bpm(h1); pa.stats_next = fp(st); pa.c1_next = (int)C1;
+  pa.M = M; pa.N = N; pa.K = K; pa.rg = rg;
+  CHECK_RC(dpe_pw_launch(&pa, dpe::PW_APPLY, cur_stream()), "pw_stream apply + next conv1");
+  return {y, bits, h1, st};
+}
+
 // The envelope of conv1x1_apply_cat: a 1x1 stride-1 downsample conv over xshape [N, H, W, Cin] (Cin in {64, 128})
 // beside a conv3 whose operand has cmid == Cin channels, both -> cout = 4 Cin.
 bool down_cat_ok(const std::vector<int64_t>& xshape, int64_t cmid, int64_t cout, int64_t stride) {
@@ -686,6 +749,11 @@ void register_bn(pybind11::module& m) {
   m.def("conv1x1_apply", &conv1x1_apply, py::arg("x"), py::arg("w"), py::arg("in_coef"), py::arg("out_coef"),
         py::arg("residual"), py::arg("res_coef") = py::none(),
         "y = relu(BN(x' W^T) + residual [BN_d]) and its ReLU bits (pre-BN tensor never stored)");
+  m.def("conv1x1_apply_next", &conv1x1_apply_next, py::arg("x"), py::arg("w"), py::arg("in_coef"), py::arg("out_coef"),
+        py::arg("residual"), py::arg("res_coef"), py::arg("w_next"), py::arg("outs") = py::none(),
+        "conv1x1_apply's (y, bits) and, from the same pass, the next conv1's h1 = y W_next^T with its BN-forward partials");
+  m.def("c1_fuse_ok", &c1_fuse_ok, py::arg("h2_shape"), py::arg("cout3"), py::arg("c1_next"),
+        "conv1x1_apply_next's envelope: conv3 64 -> 256 beside a 1x1 stride-1 conv1 256 -> {64, 128}; no CU budget");
   m.def("conv1x1_apply_cat", &conv1x1_apply_cat, py::arg("x"), py::arg("w"), py::arg("in_coef"), py::arg("out_coef"),
         py::arg("x2"), py::arg("w2"), py::arg("coef2"),
         "y = relu(BN3(x' W^T) + BN_d(x2 W2^T)) over the concatenated K and its ReLU bits (no pre-BN tensors)");

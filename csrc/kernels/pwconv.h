@@ -47,6 +47,12 @@ struct PwArgs {
   const uint16_t* x2;        // [M][cat_k2] bf16
   const uint16_t* w2;        // [N][cat_k2] bf16
   int cat_k2;
+  // PW_APPLY with the next block's conv1 formed from the rows this pass stores (K = 64, N = 256, a plain residual):
+  // c1_next in {64, 128} output channels; 0 = none
+  const uint16_t* w_next;    // [c1_next][N] bf16: the next conv1's weight
+  uint16_t* y_next;          // [M][c1_next] bf16: h1 = y . w_next^T, rounded once
+  float* stats_next;         // [2][c1_next][rg]: BatchNorm-forward (sum, sum of squares) of the stored h1, as PW_FWD's stats
+  int c1_next;
 };
 
 // The concatenated-K data grad of the Gram-path BN3 backward (bngram.hip) on a streaming kernel:
@@ -88,4 +94,9 @@ extern "C" int dpe_pw_cat_fwd_rowgroups(int64_t M, int64_t N, int64_t k2);
 // ((K, k2) in {(64, 64), (128, 64), (128, 128)} inside PW_DSUM's own).  The launch is dpe_pw_launch with
 // p_k2 = k2 and rg from here; dpe_pw_p_reduce then sums the slabs in row-group order: P[N][k2] fp32.
 extern "C" int dpe_pw_p_rowgroups(int64_t M, int64_t N, int64_t K, int64_t k2);
+// PW_APPLY with the next conv1 (PwArgs::w_next): row groups of that launch, or 0 outside its envelope (K = 64,
+// N = 256, c1 in {64, 128}; static schedule only, so 0 while a CU budget is in force with the dynamic schedule on --
+// the caller then makes the two separate calls).  The launch is dpe_pw_launch with c1_next = c1 and rg from here.
+extern "C" int dpe_pw_next_rowgroups(int64_t M, int64_t N, int64_t K, int64_t c1);
+
 extern "C" int dpe_pw_p_reduce(const float* slab, int rg, int64_t n, float* P, hipStream_t stream);

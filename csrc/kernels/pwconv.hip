@@ -84,7 +84,15 @@ DPE_DEVICE bf16x8 p_trfrag(const char* a1, const char* a2) {
 // fp32 slab per row group -- the BN3 Gram backward's dz3^T a2 without re-reading dz3.  <64, 32, 4> with
 // K2 = 64 keeps the plain kernel's 3 blocks per CU (167 VGPRs), so a launch has the same row groups and
 // partials with or without P.
-template <int K, int WN, int NS, int EPI, bool DYN = false, int K2 = 0>
+// C1 > 0 (PW_APPLY at K = 64, WN = 64: one block holds all 256 output channels of its rows; a compile-time variant
+// likewise): the pass also forms the NEXT block's conv1 output h1 = y . W1^T [M][C1] from the rows it stores.  Per
+// 32-row half every wave writes the stored bf16 values back into its staged rows (rows past M zeroed); behind a
+// barrier wave w computes h1's channels w C1/4 .. over the full K = 256 from all four staging regions (the staged
+// 16-B chunks are the MFMA B operand as they lie; W1's slice stays in VGPRs as the A operand), rounds once to bf16
+// and stages it; behind a second barrier the block stores h1 as whole rows (16-B chunks, one instruction = 1 KiB)
+// and takes BN1's forward sums of the stored values, flushed once per row group as [2][C1][row groups] --
+// PW_FWD's stats contract.  y and its bits are computed exactly as without C1.
+template <int K, int WN, int NS, int EPI, bool DYN = false, int K2 = 0, int C1 = 0>
 __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN))) ? 3 : 2) void pw_stream_kernel(PwArgs a) {
   constexpr int KC = K / 32;                  // 32-deep K chunks
   constexpr int TILE = BM * K * 2;            // bytes of one x tile in LDS ([KC][64 rows][64 B])
@@ -97,8 +105,13 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   constexpr int STG = 32 * ROWB;
   // stores outstanding per wave per tile, for the counted vmcnt below (the epilogue's operand
   // loads are consumed -- waited for -- inside the tile, so they are not outstanding here)
-  constexpr int S = (EPI == PW_APPLY || EPI == PW_CAT ? 4 : 2) * NPS;  // (PW_APPLY / PW_CAT: the y chunk and its ReLU-mask byte)
-  constexpr int VM = (NS - 1) * S + (NS - 2) * P;
+  constexpr bool NX = C1 > 0;
+  static_assert(!NX || (EPI == PW_APPLY && K == 64 && WN == 64 && K2 == 0 && !DYN && (C1 == 64 || C1 == 128)), "next conv1: envelope");
+  constexpr int HP = NX ? C1 / 64 : 0;  // NX: h1 row-chunk stores per wave per half
+  constexpr int S = (EPI == PW_APPLY || EPI == PW_CAT ? 4 : 2) * NPS + 2 * HP;  // (PW_APPLY / PW_CAT: the y chunk and its ReLU-mask byte)
+  // (NX with C1 = 128 has 64 ops behind a tile in steady state, one past the counter's range: 63 is stricter by
+  // one store of the oldest tile)
+  constexpr int VM = (NX && (NS - 1) * S + (NS - 2) * P > 63) ? 63 : (NS - 1) * S + (NS - 2) * P;
   static_assert(VM < 64, "vmcnt range");
   // ONE LDS object: ring, staging, in_coef's [scale | shift] of the K input channels, the claim slot.  (With a
   // second __shared__ object the compiler cannot tell the ring DMA's LDS writes from the other accesses and
@@ -113,8 +126,10 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   constexpr bool PF = K2 > 0 && !CAT;
   static_assert(!PF || (EPI == PW_DSUM && WN == 32 && (K2 == 64 || K2 == 128) && K2 <= K), "fused P: envelope");
   // (PF: + the a2 image [64 rows][K2] bf16, 16-B chunk c of row r at c ^ 2 h(r) -- bngram.hip's layout)
+  // (NX: + the staged h1 half [32 rows][C1] bf16, padded rows, at the same offset)
   constexpr int A2OFF = NS * TILE + 4 * STG + 2 * K * 4 + 16, A2RB = 2 * (PF ? K2 : 8);
-  __shared__ __attribute__((aligned(16))) char smem[A2OFF + (PF ? BM * A2RB : 0)];
+  constexpr int H1RB = C1 * 2 + 16, HCPR = NX ? C1 / 8 : 8, HRPP = 64 / HCPR;  // h1 row pitch, chunks per row, rows per store
+  __shared__ __attribute__((aligned(16))) char smem[A2OFF + (PF ? BM * A2RB : NX ? 32 * H1RB : 0)];
   float* const bnin = (float*)(smem + NS * TILE + 4 * STG);
   int* const claim_slot = (int*)(smem + NS * TILE + 4 * STG + 2 * K * 4);
 
@@ -156,6 +171,17 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
         wf[ni][kc] = __builtin_bit_cast(bf16x8, v);
       }
     }
+  // NX: W1 as MFMA A operands: w1f[ni][kc] = W1[c0w + 16 ni + li][32 kc + 8 g .. +7], the wave's C1 / 4 channels of h1
+  constexpr int NI2 = NX ? C1 / 64 : 1, KCN = NX ? 4 * WN / 32 : 1;
+  const int c0w = wid * (C1 / 4);
+  bf16x8 w1f[NI2][KCN];
+  if constexpr (NX) {
+#pragma unroll
+    for (int ni = 0; ni < NI2; ++ni)
+#pragma unroll
+      for (int kc = 0; kc < KCN; ++kc)
+        w1f[ni][kc] = __builtin_bit_cast(bf16x8, *(const u32x4*)(a.w_next + (int64_t)(c0w + 16 * ni + li) * (4 * WN) + 32 * kc + 8 * g));
+  }
   // BatchNorm-backward coefficients of the lane's 8 channels
   float bsc[8], bsh[8], bmu[8];
   const bool bnb = EPI == PW_DSUM || (EPI == PW_DGRAD && a.st_x != nullptr);
@@ -195,6 +221,12 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   float s[8], ss[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
+  // NX: BN1's forward sums of the h1 chunks this lane stores (channels 8 (lane % HCPR) .. +7)
+  float hs[NX ? 8 : 1], hss[NX ? 8 : 1];
+  if constexpr (NX) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { hs[e] = 0.f; hss[e] = 0.f; }
+  }
   // PF: the wave's P[32 columns][K2] as NI x K2/16 MFMA fragments; the a2 image as PCPR 1-KiB DMA pieces of
   // PRPP rows, PPW per wave (lane: row l / PCPR of the piece, physical chunk l % PCPR), each transformed by
   // the lanes that loaded it
@@ -213,8 +245,8 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
     for (int e = 0; e < 8; ++e) {
       osc[e] = a.out_coef[nch + e];
       osh[e] = a.out_coef[N + nch + e];
-      rsc[e] = a.res_coef ? a.res_coef[nch + e] : 1.f;
-      rsh[e] = a.res_coef ? a.res_coef[N + nch + e] : 0.f;
+      rsc[e] = (!NX && a.res_coef) ? a.res_coef[nch + e] : 1.f;  // (NX: a plain residual only -- dpe_pw_launch)
+      rsh[e] = (!NX && a.res_coef) ? a.res_coef[N + nch + e] : 0.f;
     }
   }
   // residual element offset of output row m (chunk nch); -1: no residual term at this row (the odd
@@ -243,6 +275,7 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
   const __amdgpu_buffer_rsrc_t smrs = rsrc(a.st_mask, (bnb && a.st_mask) ? mbytes : 0u);
   const __amdgpu_buffer_rsrc_t obrs = rsrc(a.out_bits, ((EPI == PW_APPLY || CAT) && a.out_bits) ? mbytes : 0u);
   const __amdgpu_buffer_rsrc_t psrs = rsrc(a.p_src, PF ? (uint32_t)((int64_t)M * K2 * 2) : 0u);
+  const __amdgpu_buffer_rsrc_t h1rs = rsrc(a.y_next, NX ? (uint32_t)((int64_t)M * C1 * 2) : 0u);
 
   if (!DG && a.in_coef) {  // before the ring's first DMA (its counted waits start after this)
     for (int i = tid; i < 2 * KS; i += 256) bnin[i] = a.in_coef[i];
@@ -276,7 +309,7 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
     // in the epilogue they stalled each half for a full HBM round trip).  They are older than the
     // stage's DMAs, so the compiler's wait for them leaves the ring's counted vmcnt intact.  The
     // wider-WN tiles have no registers for it (they would spill).
-    constexpr bool HOIST = (EPI != PW_FWD) && (WN == 32);
+    constexpr bool HOIST = (EPI != PW_FWD) && (WN == 32 || NX);
     constexpr bool HLD = HOIST && !CAT;  // (PW_CAT: unconditional buffer stores as the hoisted forms, no operand loads)
     constexpr int HN = HLD ? NPS : 1;
     u32x4 hrv[2][HN], hxv[2][HN];
@@ -353,8 +386,10 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) acc2[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    // (NX: each 32-row half's MFMAs at the head of its epilogue below -- the same sums in the same order, with half
+    // the accumulators live beside W1's fragments)
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) {
+    for (int kc = 0; kc < (NX ? 0 : KC); ++kc) {
       bf16x8 xf[MI];
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) xf[mi] = kfrag(img + kc * (BM * 64), 16 * mi);
@@ -402,6 +437,19 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
     char* stg = smem + NS * TILE + wid * STG;
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
+      if constexpr (NX) {
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) {
+          bf16x8 xf[2];
+#pragma unroll
+          for (int mh = 0; mh < 2; ++mh) xf[mh] = kfrag(img + kc * (BM * 64), 16 * (2 * hf + mh));
+#pragma unroll
+          for (int mh = 0; mh < 2; ++mh)
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni)
+              acc[2 * hf + mh][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ni][kc], xf[mh], acc[2 * hf + mh][ni], 0, 0, 0);
+        }
+      }
       // the half's epilogue operands first: their latency overlaps the staging below
       u32x4 rv[NPS], xv[NPS];
       uint32_t rmb[NPS], smb[NPS];
@@ -464,7 +512,7 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             float t = fmaf(f[e], osc[e], osh[e]);
-            if (a.residual) t += a.res_coef ? bf2f(f2bf(fmaf(r[e], rsc[e], rsh[e]))) : r[e];
+            if (a.residual) t += (!NX && a.res_coef) ? bf2f(f2bf(fmaf(r[e], rsc[e], rsh[e]))) : r[e];
             f[e] = fmaxf(t, 0.f);
           }
           v = pack8(f);
@@ -518,7 +566,57 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
         if constexpr (HOIST) __builtin_amdgcn_raw_buffer_store_b128(v, yrs, valid ? (uint32_t)(((int64_t)m * N + nch) * 2) : OOB, 0, 0);
         else if (valid) *(u32x4*)(a.y + (int64_t)m * N + nch) = v;
         // PF: the stored value (after the residual, the mask and the rounding) back into the staged row
-        if constexpr (PF) *(u32x4*)(stg + row * ROWB + ch * 16) = valid ? v : u32x4{0u, 0u, 0u, 0u};
+        if constexpr (PF || NX) *(u32x4*)(stg + row * ROWB + ch * 16) = valid ? v : u32x4{0u, 0u, 0u, 0u};
+      }
+      if constexpr (NX) {
+        // h1_half^T[C1][32 rows] = W1 . y_half^T: the wave's C1 / 4 channels over all 256 channels of y, B operand =
+        // row 16 mi + li, channels 32 kc + 8 g .. +7 of the staged rows (wave kc / 2's region) as they lie
+        lds_barrier();  // every wave's stored values are back in its staged rows
+        f32x4 hacc[2][NI2];
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < NI2; ++ni) hacc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const char* const sall = smem + NS * TILE;
+#pragma unroll
+        for (int kc = 0; kc < KCN; ++kc)
+#pragma unroll
+          for (int mi = 0; mi < 2; ++mi) {
+            const bf16x8 yf = __builtin_bit_cast(
+                bf16x8, *(const u32x4*)(sall + (kc >> 1) * STG + (16 * mi + li) * ROWB + ((kc & 1) * 32 + 8 * g) * 2));
+#pragma unroll
+            for (int ni = 0; ni < NI2; ++ni)
+              hacc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[ni][kc], yf, hacc[mi][ni], 0, 0, 0);
+          }
+        // rounded once and staged: lane holds channels c0w + 16 ni + 4 g + e of row 16 mi + li
+        char* const h1s = smem + A2OFF;
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < NI2; ++ni) {
+            u32x2 pk;
+            pk[0] = pack_bf2(hacc[mi][ni][0], hacc[mi][ni][1]);
+            pk[1] = pack_bf2(hacc[mi][ni][2], hacc[mi][ni][3]);
+            *(u32x2*)(h1s + (16 * mi + li) * H1RB + (c0w + 16 * ni + 4 * g) * 2) = pk;
+          }
+        // (every wave is then also past its reads of the other waves' staged rows: the next half may overwrite them)
+        lds_barrier();
+        // whole rows: wave w stores rows 8 w .. + 7 of the half, HRPP rows per instruction; the sums are of the
+        // stored values (rows past M: exact zeros -- their y rows were zeroed above)
+#pragma unroll
+        for (int p = 0; p < HP; ++p) {
+          const int row = 8 * wid + p * HRPP + lane / HCPR, hch = lane % HCPR;
+          const u32x4 v = *(const u32x4*)(h1s + row * H1RB + hch * 16);
+          const int m = m0 + 32 * hf + row;
+          __builtin_amdgcn_raw_buffer_store_b128(v, h1rs, m < M ? (uint32_t)(((int64_t)m * C1 + hch * 8) * 2) : OOB, 0, 0);
+          float f[8];
+          unpack8(v, f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            hs[e] += f[e];
+            hss[e] = fmaf(f[e], f[e], hss[e]);
+          }
+        }
       }
       if constexpr (PF) {
         // P += y_half^T a2_half: K = the half's 32 rows, one MFMA step per fragment
@@ -570,6 +668,29 @@ __global__ __launch_bounds__(256, (K == 64 && (EPI == PW_FWD || (K2 > 0 && !DYN)
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) { s[e] = 0.f; ss[e] = 0.f; }
+    }
+    if constexpr (NX) {
+      // h1's sums: over the lanes holding the same chunk, then over the four waves (in order) through LDS
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+#pragma unroll
+        for (int o = HCPR; o < 64; o <<= 1) {
+          hs[e] += __shfl_xor(hs[e], o, 64);
+          hss[e] += __shfl_xor(hss[e], o, 64);
+        }
+      }
+      float* const red = (float*)(smem + A2OFF);  // [4 waves][2][C1] over the h1 staging rows (32 C1 <= 32 H1RB bytes)
+      __syncthreads();  // every wave is past its last reads of them
+      if (lane < HCPR) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          red[wid * 2 * C1 + 8 * lane + e] = hs[e];
+          red[wid * 2 * C1 + C1 + 8 * lane + e] = hss[e];
+        }
+      }
+      __syncthreads();
+      if (tid < 2 * C1)
+        a.stats_next[(int64_t)tid * RG + col] = ((red[tid] + red[2 * C1 + tid]) + red[4 * C1 + tid]) + red[6 * C1 + tid];
     }
     if constexpr (PF) {
       // the row group's slab [N][K2] (a row group without tiles stores zeros) and a fresh accumulator: lane
@@ -934,13 +1055,13 @@ static int pw_wn(int K, int epi) {
 // Every block carries the same number of tiles, so the grid must be exactly the resident
 // capacity (blocks per CU from the occupancy API x CUs): a grid that lets the dispatcher put
 // 3 blocks on some CUs and 1 on others finishes at the pace of the fullest CU.
-template <int K, int WN, int NS, int EPI, bool DYN, int K2 = 0>
+template <int K, int WN, int NS, int EPI, bool DYN, int K2 = 0, int C1 = 0>
 static int pw_slots() {
   static int slots = [] {
     int dev = 0, cus = 0, per = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pw::pw_stream_kernel<K, WN, NS, EPI, DYN, K2>, 256, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pw::pw_stream_kernel<K, WN, NS, EPI, DYN, K2, C1>, 256, 0);
     return std::max(1, per) * std::max(1, cus);
   }();
   return slots;
@@ -1032,6 +1153,21 @@ static PwPlan pw_plan(int64_t M, int64_t N, int64_t K, int epi, int64_t k2 = 0) 
   return {(int)rg, (int)rg};
 }
 
+// PW_APPLY with the next conv1 (c1 output channels): 64 columns per wave, so one block spans all N = 256 output
+// channels of its rows and a row group is one block.  Static schedule only: outside the envelope while a CU budget
+// is in force with the dynamic schedule on (the caller takes the separate calls), as fused P with 128 columns.
+static int pw_plan_next(int64_t M, int64_t N, int64_t K, int64_t c1) {
+  if (K != 64 || N != 256 || (c1 != 64 && c1 != 128)) return 0;
+  if (M <= 0 || M * N >= (1ll << 31) - 256) return 0;
+  const int reserve = dpe_cu_reserve();
+  if (reserve > 0 && pw_dynamic()) return 0;
+  const int cap = c1 == 64 ? pw_slots<64, 64, 4, PW_APPLY, false, 0, 64>() : pw_slots<64, 64, 4, PW_APPLY, false, 0, 128>();
+  const int64_t tiles = (M + pw::BM - 1) / pw::BM;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(cap - reserve, tiles));
+}
+
+extern "C" int dpe_pw_next_rowgroups(int64_t M, int64_t N, int64_t K, int64_t c1) { return pw_plan_next(M, N, K, c1); }
+
 extern "C" int dpe_pw_rowgroups(int64_t M, int64_t N, int64_t K, int epi) { return pw_plan(M, N, K, epi).rg; }
 
 extern "C" int dpe_pw_cat_fwd_rowgroups(int64_t M, int64_t N, int64_t k2) {
@@ -1080,6 +1216,17 @@ extern "C" int dpe_pw_launch(const PwArgs* args, int epi, hipStream_t st) {
   const PwArgs& a = *args;
   if (a.p_k2 < 0 || (a.p_k2 > 0 && (epi != PW_DSUM || !a.p_src || !a.p_slab))) return -1;
   if ((epi == PW_CAT) != (a.cat_k2 > 0) || (epi == PW_CAT && a.p_k2 > 0)) return -1;
+  if (a.c1_next != 0) {
+    // the next conv1 beside the output: PW_APPLY with a plain residual, every operand and output present
+    if (epi != PW_APPLY || a.p_k2 != 0 || !a.w_next || !a.y_next || !a.stats_next || !a.out_coef || !a.residual || a.res_coef ||
+        !a.out_bits || a.st_x || a.stats || a.res_h > 0)
+      return -1;
+    if (a.rg <= 0 || a.rg != pw_plan_next(a.M, a.N, a.K, a.c1_next)) return -1;
+    const dim3 grid((unsigned)a.rg), block(256);
+    if (a.c1_next == 64) hipLaunchKernelGGL((pw::pw_stream_kernel<64, 64, 4, PW_APPLY, false, 0, 64>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((pw::pw_stream_kernel<64, 64, 4, PW_APPLY, false, 0, 128>), grid, block, 0, st, a);
+    return 0;
+  }
   const int64_t k2 = epi == PW_CAT ? a.cat_k2 : a.p_k2;
   if (a.rg <= 0 || a.rg != pw_plan(a.M, a.N, a.K, epi, k2).rg) return -1;
   if (epi == PW_CAT && (!a.x2 || !a.w2 || !a.out_coef || !a.res_coef || !a.out_bits || a.residual || a.st_x || a.stats ||

@@ -82,6 +82,18 @@ pass over x and its pilot run before conv3.  The static and the dynamic-schedule
 CU budget the path stays as it is (no fall-back to the separate calls is needed).  Eval / no-grad forwards,
 defer_out / DPE_AX_FWD and the non-Gram paths are unchanged; DPE_DOWN_CAT=0 makes today's calls bit for bit.
 
+The next block's conv1 inside conv3's streaming pass (DPE_C1_FUSE=1; identity blocks on the BN3 Gram path whose conv3
+is 64 -> 256 and whose successor's conv1 is a 1x1 stride-1 conv to 64 or 128 channels -- ResNet-50's layer1.1 ->
+layer1.2 and layer1.2 -> layer2.0; training forward): the pass that forms out_i holds every output row, rounded to
+bf16, in LDS on the way to the store, so it also computes h1_{i+1} = out_i W1^T from those rows (conv1x1_apply_next;
+pwconv.hip, the C1 variant: 64 columns per wave so one block spans all 256 channels, a second MFMA step per 32-row
+half, h1 rounded once and stored as whole rows, BN1's forward sums of the stored values per row group).  Block i+1
+receives (h1, sums) through the link's ``h1_next`` field and skips only its own conv1 launch: out_i IS written, so
+every other path of block i+1 (Gram, down_cat, on-load BN1, the backward and its conv1 weight grad over out_i) is
+as without the flag.  out_i and its bits are bit for bit conv1x1_apply's; h1 differs from conv_fwd's by the fp32
+summation order only.  No dynamic-schedule variant is built: under a CU budget c1_fuse_ok is false and the two
+separate calls run.  DPE_C1_FUSE=0 makes today's calls bit for bit.
+
 Weight gradients are accumulated straight into the DDP bucket views and each
 parameter is announced to the reducer as soon as its gradient is final, in
 reverse-forward order, so bucket all-reduces start while earlier blocks are
@@ -159,6 +171,12 @@ _PW_FUSED_P = _GRAM and os.environ.get("DPE_PW_FUSED_P", "1") != "0"
 # Gram backward does not (bnd_gram_ok fails, or the switch is flipped in-process for an A/B of the backward alone),
 # the forward is the same fused pass and hd is produced beside it for the backward only.
 _DOWN_CAT =_BND_GRAM and os.environ.get("DPE_DOWN_CAT", "1") != "0"
+# DPE_C1_FUSE=0: the next block's conv1 as its own launch over the stored block output (bit for bit the calls before
+# the fused form; A/B reference).  On: formed inside conv3's streaming pass from the rows it stores
+# (conv1x1_apply_next, pwconv.hip) where c1_fuse_ok holds -- identity blocks with a 64 -> 256 conv3 ahead of a 1x1
+# stride-1 conv1 to 64 / 128 channels (ResNet-50: layer1.1 -> layer1.2 -> layer2.0).  Training forward, Gram path,
+# chained blocks only.  Measurements: docs/perf_notes.md.
+_C1_FUSE = _GRAM and os.environ.get("DPE_C1_FUSE", "1") != "0"
 
 
 def _ax_ok(conv, cin) -> bool:
@@ -183,7 +201,7 @@ class _BN3Link:
     fused-epilogue result (BN3_i partials, identity of the masked dz3_i)
     handed back to block i's backward."""
 
-    __slots__ = ("h3", "coef", "mask", "part", "dz_ptr", "dz_shape", "pending", "gram", "psrc", "P")
+    __slots__ = ("h3", "coef", "mask", "part", "dz_ptr", "dz_shape", "pending", "gram", "psrc", "P", "h1_next")
 
     def __init__(self):
         self.h3 = self.coef = self.mask = self.part = None
@@ -195,6 +213,9 @@ class _BN3Link:
         # (h3, coef3, idn, idn_coef, out, bits): block i's output, allocated but not yet written --
         # block i+1's conv1 writes it (conv1x1_bnin_fwd)
         self.pending = None
+        # (h1, BN1 partials, out, block i+1): block i+1's conv1 output, formed by the pass that WROTE block i's output
+        # (DPE_C1_FUSE) -- unlike ``pending`` the output exists, and block i+1 only skips its conv1 launch
+        self.h1_next = None
 
 
 def _conv_conf(conv):
@@ -203,7 +224,7 @@ def _conv_conf(conv):
 
 class BottleneckFn(Function):
     @staticmethod
-    def forward(ctx, x, block, link_in, link_out, defer_out, gram_next, *params):
+    def forward(ctx, x, block, link_in, link_out, defer_out, gram_next, next_block, *params):
         C = ext()
         convs = [block.c1, block.c2, block.c3] + ([block.down] if block.down is not None else [])
         ws = [shadow(cb.conv.weight) for cb in convs]
@@ -217,12 +238,20 @@ class BottleneckFn(Function):
             h1_st = C.conv1x1_bnin_fwd(ph3, pidn, pc3, pcd, ws[0], x, pbits, True, _AX_TILE)
         else:
             h1_st = None
+        # conv1's output came with the previous block's output (DPE_C1_FUSE): x is written, nothing else changes
+        h1_pre = None
+        if link_in is not None and link_in.h1_next is not None:
+            nh1, nst, nout, nblk = link_in.h1_next
+            link_in.h1_next = None
+            assert nout is x and nblk is block, "fused conv1 output consumed by a different tensor or block"
+            h1_pre = (nh1, nst)
+        h1_done = h1_st if h1_st is not None else h1_pre
 
         def convbn(i, inp, relu, residual=None):
             cb = convs[i]
             s, p, d = _conv_conf(cb.conv)
-            if i == 0 and h1_st is not None:
-                h, st = h1_st
+            if i == 0 and h1_done is not None:
+                h, st = h1_done
             else:
                 h, st = C.conv_fwd(inp, ws[i], s, p, d, True, None)  # BN stats partials from the epilogue
             bn = cb.bn
@@ -233,8 +262,8 @@ class BottleneckFn(Function):
         def conv_coef(i, inp, in_coef=None):
             cb = convs[i]
             s, p, d = _conv_conf(cb.conv)
-            if i == 0 and h1_st is not None:
-                h, st = h1_st
+            if i == 0 and h1_done is not None:
+                h, st = h1_done
             else:
                 h, st = C.conv_fwd(inp, ws[i], s, p, d, True, None, in_coef)
             bn = cb.bn
@@ -264,6 +293,12 @@ class BottleneckFn(Function):
         down_cat = bool(use_gram and _DOWN_CAT and dconv is not None and tuple(dconv.kernel_size) == (1, 1)
                         and tuple(dconv.padding) == (0, 0) and tuple(dconv.stride) == (1, 1)
                         and C.down_cat_ok(list(x.shape), h2_shape[3], dconv.out_channels, 1))
+        # ... and the next block's conv1 inside conv3's pass (DPE_C1_FUSE): identity blocks (a plain residual)
+        c1n = next_block.c1.conv if next_block is not None else None
+        c1_fuse = bool(use_gram and _C1_FUSE and c1n is not None and block.down is None and gram_next
+                       and tuple(c1n.kernel_size) == (1, 1) and tuple(c1n.stride) == (1, 1)
+                       and tuple(c1n.padding) == (0, 0) and c1n.in_channels == out_shape[3] and c1n.out_channels == abs(gram_next)
+                       and C.c1_fuse_ok(h2_shape, out_shape[3], c1n.out_channels))
         if h1_st is None and block.down is not None and not down_cat:
             hd, cd = conv_coef(3, x)  # BN_d is applied inside BN3's pass (bn_apply with residual_coef)
         else:
@@ -319,6 +354,11 @@ class BottleneckFn(Function):
                     hd = C.conv_fwd(x, ws[3], *_conv_conf(dconv), False, None)[0]
             elif block.down is not None:
                 out, bits = C.conv1x1_apply(src, ws[2], src_coef, c3, hd, cd)
+            elif c1_fuse:
+                # the same pass also forms the next block's h1 = out W1^T and BN1's partials from the rows it stores
+                # (no note_use: the next block counts its own weight's single backward write)
+                out, bits, nh1, nst = C.conv1x1_apply_next(src, ws[2], src_coef, c3, x, None, shadow(c1n.weight))
+                link_out.h1_next = (nh1, nst, out, next_block)
             else:
                 out, bits = C.conv1x1_apply(src, ws[2], src_coef, c3, x, None)
             h3 = None
@@ -639,7 +679,7 @@ class BottleneckFn(Function):
                 dhd, _ = bn_bwd(3, dz3, None, hd, cd, False)
             wgrad(3, dhd, x)
         pgrads = [grads.get(id(p)) for p in ctx.block._fused_params]
-        return (dx, None, None, None, None, None, *pgrads)
+        return (dx, None, None, None, None, None, None, *pgrads)
 
 
 def gram_successor_width(nxt) -> int:
@@ -660,13 +700,15 @@ def gram_successor_width(nxt) -> int:
     return c1.out_channels
 
 
-def bottleneck_forward(block, x, link_in=None, chain=False, count_batches=True, defer_out=False, gram_next=0):
+def bottleneck_forward(block, x, link_in=None, chain=False, count_batches=True, defer_out=False, gram_next=0,
+                       next_block=None):
     """Fused block forward.  ``chain=True`` (the ResNet's own block loop, where
     this block's output feeds only the next block) returns ``(out, link)`` for
     the next block's ``link_in``.  ``count_batches=False``: the ResNet advanced
     every block's num_batches_tracked in one launch already.  ``defer_out`` (with
     ``chain``; the next block passes ``can_materialise_input``): the returned
-    output is written by the next block's conv1, which MUST be called next."""
+    output is written by the next block's conv1, which MUST be called next.  ``next_block`` (with ``chain``): the
+    fused block this output feeds next, whose conv1 this block's conv3 pass may compute (DPE_C1_FUSE)."""
     params = block._fused_params
     if count_batches:
         nbt = [cb.bn.num_batches_tracked
@@ -674,5 +716,6 @@ def bottleneck_forward(block, x, link_in=None, chain=False, count_batches=True, 
         torch._foreach_add_(nbt, 1)
     link_out = _BN3Link() if (chain and _BN3_CHAIN) else None
     out = BottleneckFn.apply(x, block, link_in if _BN3_CHAIN else None, link_out, bool(defer_out and link_out is not None),
-                             int(gram_next) if link_out is not None else 0, *params)
+                             int(gram_next) if link_out is not None else 0,
+                             next_block if link_out is not None else None, *params)
     return (out, link_out) if chain else out

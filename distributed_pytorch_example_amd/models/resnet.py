@@ -59,15 +59,16 @@ class Bottleneck(nn.Module):
     def forward(self, x):
         return self.forward_chained(x, None, chain=False)
 
-    def forward_chained(self, x, link=None, chain=True, count_batches=True, defer_out=False, gram_next=0):
+    def forward_chained(self, x, link=None, chain=True, count_batches=True, defer_out=False, gram_next=0, next_block=None):
         """``chain=True``: returns (out, link); the link lets the next block's
         backward fuse this block's BN3 backward (``_resnet_fused``).
         ``count_batches=False``: the caller already advanced the BNs' num_batches_tracked.
-        ``defer_out``: the output is written by the next block's conv1 (called next)."""
+        ``defer_out``: the output is written by the next block's conv1 (called next).
+        ``next_block``: the fused block that consumes this output next (its conv1 may run inside this block's conv3 pass)."""
         if x.is_cuda and self.training and self.fused:
             from ._resnet_fused import bottleneck_forward
 
-            return bottleneck_forward(self, x, link, chain, count_batches, defer_out, gram_next)
+            return bottleneck_forward(self, x, link, chain, count_batches, defer_out, gram_next, next_block)
         out = self._forward_per_op(x)
         return (out, None) if chain else out
 
@@ -150,8 +151,10 @@ class ResNet(nn.Module):
 
             gram = [gram_successor_width(self.blocks[i + 1]) if (f and i + 1 < len(fused) and fused[i + 1]) else 0
                     for i, f in enumerate(fused)]
-        for blk, f, d, gn in zip(self.blocks, fused, defer, gram):  # each block's output feeds only the next block
-            h, link = blk.forward_chained(h, link, count_batches=not f, defer_out=d, gram_next=gn)
+        # the fused successor of each fused block: its conv1 may run inside this block's conv3 pass
+        nxt = [self.blocks[i + 1] if (f and i + 1 < len(fused) and fused[i + 1]) else None for i, f in enumerate(fused)]
+        for blk, f, d, gn, nb in zip(self.blocks, fused, defer, gram, nxt):  # each block's output feeds only the next block
+            h, link = blk.forward_chained(h, link, count_batches=not f, defer_out=d, gram_next=gn, next_block=nb)
         h = Fx.global_avg_pool_nhwc(h)
         return self.fc(h)
 
