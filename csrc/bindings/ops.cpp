@@ -41,8 +41,11 @@ std::vector<Tensor> cross_entropy(const Tensor& logits, const Tensor& labels, in
 // mean and the backward scale come out of the reduction kernel itself (no torch count / clamp / divide
 // launches at the forward -> backward seam).
 // label_smoothing / z_loss (both 0: the plain kernels): see csrc/kernels/loss.hip.
+// labels2 / mix_w (together): a second label per row (ignore_index: none) and the weight of the first one, a
+// device fp32 tensor of 1 element (the batch's) or B (per row) that the kernels read -- the MIX kernels.
 std::vector<Tensor> cross_entropy_mean(const Tensor& logits, const Tensor& labels, int64_t V, bool grad_bf16,
-                                       int64_t ignore_index, bool inplace, double label_smoothing, double z_loss) {
+                                       int64_t ignore_index, bool inplace, double label_smoothing, double z_loss,
+                                       const c10::optional<Tensor>& labels2, const c10::optional<Tensor>& mix_w) {
   CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_CONTIG(labels);
   TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
   const bool in_bf16 = logits.scalar_type() == at::kBFloat16;
@@ -61,7 +64,22 @@ std::vector<Tensor> cross_entropy_mean(const Tensor& logits, const Tensor& label
   } else {
     d = at::empty(logits.sizes(), logits.options().dtype(grad_bf16 ? at::kBFloat16 : at::kFloat));
   }
-  if (label_smoothing == 0.0 && z_loss == 0.0) {
+  TORCH_CHECK(has(labels2) == has(mix_w), "cross_entropy_mean: labels2 and mix_w go together");
+  if (has(labels2)) {
+    TORCH_CHECK(V > 0 && V <= ld, "cross_entropy_mean: V must be in [1, row length]");
+    TORCH_CHECK(labels2->is_cuda() && labels2->device() == logits.device() && labels2->scalar_type() == at::kLong &&
+                    labels2->is_contiguous() && labels2->numel() == B,
+                "cross_entropy_mean: labels2 must be a contiguous int64 tensor of one label per row on the logits' device");
+    TORCH_CHECK(labels.is_cuda() && labels.device() == logits.device(), "cross_entropy_mean: labels must be on the logits' device");
+    TORCH_CHECK(mix_w->is_cuda() && mix_w->device() == logits.device() && mix_w->scalar_type() == at::kFloat &&
+                    (mix_w->numel() == 1 || (mix_w->numel() == B && mix_w->is_contiguous())),
+                "cross_entropy_mean: mix_w must be an fp32 tensor of 1 or B (contiguous) elements on the logits' device");
+    CHECK_RC(dpe_cross_entropy_mean_mix(logits.data_ptr(), in_bf16, (const int64_t*)labels.data_ptr(),
+                                        (const int64_t*)labels2->data_ptr(), fp(*mix_w), mix_w->numel() == 1 ? 0 : 1, (int)B,
+                                        (int)V, ld, 1.f, d.data_ptr(), grad_bf16, fp(rows), fp(out4), (int)ignore_index,
+                                        (float)label_smoothing, (float)z_loss, cur_stream()),
+             "cross_entropy_mean");
+  } else if (label_smoothing == 0.0 && z_loss == 0.0) {
     CHECK_RC(dpe_cross_entropy_mean(logits.data_ptr(), in_bf16, (const int64_t*)labels.data_ptr(), (int)B, (int)V, ld, 1.f,
                                     d.data_ptr(), grad_bf16, fp(rows), fp(out4), (int)ignore_index, cur_stream()),
              "cross_entropy_mean");
@@ -193,6 +211,50 @@ Tensor nchw_to_s2d(const Tensor& x) {
   TORCH_CHECK(C <= 4 && H % 2 == 0 && W % 2 == 0, "nchw_to_s2d: needs C <= 4 and even H, W");
   Tensor y = at::empty({N, H / 2, W / 2, 16}, x.options().dtype(at::kBFloat16));
   CHECK_RC(dpe_nchw_to_s2d(fp(x), bpm(y), (int)N, (int)C, (int)H, (int)W, cur_stream()), "nchw_to_s2d");
+  return y;
+}
+
+// One mixing decision per row of `count`: [count, 8] fp32 rows [w_pix, w_lab, x1, y1, x2, y2, mode, lam_raw] drawn from
+// the device state rng (int64[2] seed, offset; rows use offset, offset + 1, ...; the caller advances it by count).
+Tensor mix_draw(const Tensor& rng, int64_t stream, int64_t H, int64_t W, double mixup_alpha, double cutmix_alpha, double prob,
+                double switch_prob, int64_t count) {
+  TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == at::kLong && rng.dim() == 1 && rng.numel() == 2 && rng.is_contiguous(),
+              "mix_draw: rng must be a contiguous int64[2] GPU tensor");
+  TORCH_CHECK(stream >= 0 && stream <= 0xffffffffLL, "mix_draw: stream must fit 32 bits");
+  TORCH_CHECK(H > 0 && W > 0 && H <= 65536 && W <= 65536, "mix_draw: H and W must be in [1, 65536]");
+  TORCH_CHECK(count >= 1 && count <= (1 << 20), "mix_draw: count must be in [1, 2^20]");
+  TORCH_CHECK(mixup_alpha >= 0.0 && cutmix_alpha >= 0.0, "mix_draw: alphas must be >= 0");
+  TORCH_CHECK(prob >= 0.0 && prob <= 1.0 && switch_prob >= 0.0 && switch_prob <= 1.0, "mix_draw: probabilities must be in [0, 1]");
+  Tensor out = at::empty({count, 8}, rng.options().dtype(at::kFloat));
+  CHECK_RC(dpe_mix_draw((const int64_t*)rng.data_ptr(), (uint32_t)stream, (int)H, (int)W, (float)mixup_alpha, (float)cutmix_alpha,
+                        (float)prob, (float)switch_prob, (int)count, fp(out), cur_stream()),
+           "mix_draw");
+  return out;
+}
+
+// x NCHW fp32 mixed with x.roll(1, 0) by the row `params` (8 fp32 on the device, read by the kernel) and packed:
+// layout 0 space-to-depth [N,H/2,W/2,16] bf16, 1 NHWC bf16 padded to cpad channels.  `out`: a caller's buffer.
+Tensor mix_pack(const Tensor& x, const Tensor& params, int64_t layout, int64_t cpad, const c10::optional<Tensor>& out_) {
+  CHECK_GPU(x); CHECK_F32(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.dim() == 4, "mix_pack: x must be NCHW");
+  TORCH_CHECK(params.is_cuda() && params.device() == x.device() && params.scalar_type() == at::kFloat &&
+                  params.numel() == 8 && params.is_contiguous(),
+              "mix_pack: params must be 8 contiguous fp32 values on x's device");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(N >= 1 && C >= 1 && H >= 1 && W >= 1 && N <= 0x7fffffffLL && H * W <= 0x7fffffffLL, "mix_pack: bad shape");
+  TORCH_CHECK(layout == 0 || layout == 1, "mix_pack: layout 0 (s2d) or 1 (nhwc)");
+  std::vector<int64_t> shape;
+  const int64_t Cp = std::max<int64_t>(C, cpad);
+  if (layout == 0) {
+    TORCH_CHECK(C <= 4 && H % 2 == 0 && W % 2 == 0, "mix_pack: the s2d layout needs C <= 4 and even H, W");
+    shape = {N, H / 2, W / 2, 16};
+  } else {
+    shape = {N, H, W, Cp};
+  }
+  Tensor y = has(out_) ? *out_ : at::empty(shape, x.options().dtype(at::kBFloat16));
+  CHECK_GPU(y); CHECK_BF16(y); CHECK_CONTIG(y);
+  TORCH_CHECK(y.device() == x.device() && y.sizes().vec() == shape, "mix_pack: out must have the packed shape on x's device");
+  CHECK_RC(dpe_mix_pack(fp(x), fp(params), bpm(y), (int)N, (int)C, (int)H, (int)W, (int)layout, (int)Cp, cur_stream()), "mix_pack");
   return y;
 }
 
@@ -573,8 +635,14 @@ void register_ops(pybind11::module& m) {
   namespace py = pybind11;
   m.def("cross_entropy_mean", &cross_entropy_mean, py::arg("logits"), py::arg("labels"), py::arg("V"),
         py::arg("grad_bf16"), py::arg("ignore_index") = -100, py::arg("inplace") = false, py::arg("label_smoothing") = 0.0,
-        py::arg("z_loss") = 0.0,
-        "training CE: (out4 = [sum, correct, mean, 1/n_valid], d loss_row / d logits), optionally label-smoothed / with z-loss");
+        py::arg("z_loss") = 0.0, py::arg("labels2") = py::none(), py::arg("mix_w") = py::none(),
+        "training CE: (out4 = [sum, correct, mean, 1/n_valid], d loss_row / d logits), optionally label-smoothed / with z-loss / "
+        "with a second label per row weighted by the device tensor mix_w");
+  m.def("mix_draw", &mix_draw, py::arg("rng"), py::arg("stream"), py::arg("H"), py::arg("W"), py::arg("mixup_alpha"),
+        py::arg("cutmix_alpha"), py::arg("prob") = 1.0, py::arg("switch_prob") = 0.5, py::arg("count") = 1,
+        "mixup / cutmix decisions [count, 8] from the device rng state (not advanced)");
+  m.def("mix_pack", &mix_pack, py::arg("x"), py::arg("params"), py::arg("layout"), py::arg("cpad") = 8, py::arg("out") = py::none(),
+        "NCHW fp32 -> packed bf16 (0: s2d, 1: nhwc) of the batch mixed with its roll by the device row params");
   m.def("ce_grad_scale", &ce_grad_scale, py::arg("d"), py::arg("g"), py::arg("inv_n"), "d * g * inv_n (device scalars)");
   m.def("cross_entropy", &cross_entropy, py::arg("logits"), py::arg("labels"), py::arg("V"), py::arg("grad_scale"),
         py::arg("want_grad"), py::arg("grad_bf16"), py::arg("ignore_index") = -100, py::arg("inplace") = false);

@@ -86,7 +86,17 @@ int dpe_cross_entropy_mean(const void* logits, int in_bf16, const int64_t* label
 int dpe_cross_entropy_mean_reg(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
                                float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* out4,
                                int ignore_index, float eps, float zl, hipStream_t st);
+// two labels per row (the MIX instantiations): labels2[row] == ignore_index means no partner; the weight of
+// labels[row] is w[row * w_stride] (w_stride 0: one weight for the batch, 1: one per row), read on the device
+int dpe_cross_entropy_mean_mix(const void* logits, int in_bf16, const int64_t* labels, const int64_t* labels2, const float* w,
+                               int w_stride, int B, int V, int64_t ld, float grad_scale, void* dlogits, int out_bf16,
+                               float* loss_rows, float* out4, int ignore_index, float eps, float zl, hipStream_t st);
 int dpe_ce_grad_scale(const void* d, void* o, int64_t n, int bf16, const float* g, const float* inv_n, hipStream_t st);
+// ---- mix.hip
+int dpe_mix_draw(const int64_t* rng, uint32_t stream, int H, int W, float mixup_alpha, float cutmix_alpha, float prob,
+                 float switch_prob, int count, float* out, hipStream_t st);
+int dpe_mix_pack(const float* x, const float* prm, uint16_t* y, int N, int C, int H, int W, int layout, int Cp,
+                 hipStream_t st);
 // ---- eltwise.hip
 int dpe_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t st);
 int dpe_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, hipStream_t st);

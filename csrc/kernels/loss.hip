@@ -14,6 +14,13 @@
 // with one more per-thread accumulator, sum_{j<V}(z_j - m), in the pass that sums the exponentials: the
 // terms are bounded by the row's range and nothing cancels against V * m.  No further pass over the row.
 // The REG = false instantiations are the plain kernels, instruction for instruction.
+//
+// MIX (compile-time, next to REG; arguments in a trailing CeMix<MIX>, empty without it) gives a row two labels, y with
+// weight w and y2 with weight 1 - w (mixup / cutmix targets): z_y becomes zmix = w z_y + (1 - w) z_y2 in the loss and
+//   d/dz_j = ... - (1 - eps) w [j = y] - (1 - eps)(1 - w) [j = y2]                  (the two terms add when y = y2)
+// w is read from device memory (one per batch or one per row).  A row is ignored iff labels[row] is ignore_index;
+// labels2[row] == ignore_index is a row without partner, computed with w = 1.  The MIX = false instantiations are
+// the kernels as they were, instruction for instruction (docs/perf_notes.md, "Mixup / CutMix").
 #include <algorithm>
 #include <type_traits>
 
@@ -37,11 +44,39 @@ struct CeReg<true> {
   float eps, zl;
 };
 
-template <typename TIn, typename TOut, bool REG>
+// The MIX arm's arguments; empty without it.
+template <bool MIX>
+struct CeMix {};
+template <>
+struct CeMix<true> {
+  const int64_t* labels2;
+  const float* w;
+  int w_stride;
+};
+
+// (label2, w) of a row: no partner (labels2[row] == ignore_index) is w = 1 on the row's own label.  Nothing without MIX.
+template <bool MIX>
+struct CeMixRow {};
+template <>
+struct CeMixRow<true> {
+  int64_t label2;
+  float w;
+  DPE_DEVICE void init(const CeMix<true>& mx, int row, int64_t label, int ignore_index) {
+    label2 = label;
+    w = 1.f;
+    const int64_t l2 = mx.labels2[row];
+    if (l2 != ignore_index) {
+      label2 = l2;
+      w = mx.w[(int64_t)row * mx.w_stride];
+    }
+  }
+};
+
+template <typename TIn, typename TOut, bool REG, bool MIX>
 __global__ __launch_bounds__(1024) void ce_kernel(const TIn* __restrict__ logits, const int64_t* __restrict__ labels, int B,
                                                  int V, int64_t ld, float grad_scale, TOut* __restrict__ dlogits,
                                                  float* __restrict__ loss_rows, float* __restrict__ loss_sum,
-                                                 float* __restrict__ correct, int ignore_index, CeReg<REG> ra) {
+                                                 float* __restrict__ correct, int ignore_index, CeReg<REG> ra, CeMix<MIX> mx) {
   __shared__ float sh[32];
   __shared__ int shi[32];
   const int row = blockIdx.x;
@@ -50,7 +85,15 @@ __global__ __launch_bounds__(1024) void ce_kernel(const TIn* __restrict__ logits
   const bool ignored = (label == ignore_index);
   // z_y read up front (before any thread can overwrite it when dlogits aliases logits)
   __shared__ float s_zy;
-  if (threadIdx.x == 0) s_zy = (label >= 0 && label < V) ? ldv<TIn>(z, label) : 0.f;
+  [[maybe_unused]] CeMixRow<MIX> mr;
+  if constexpr (MIX) mr.init(mx, row, label, ignore_index);
+  if constexpr (MIX) {
+    if (threadIdx.x == 0)
+      s_zy = mr.w * ((label >= 0 && label < V) ? ldv<TIn>(z, label) : 0.f) +
+             (1.f - mr.w) * ((mr.label2 >= 0 && mr.label2 < V) ? ldv<TIn>(z, mr.label2) : 0.f);
+  } else {
+    if (threadIdx.x == 0) s_zy = (label >= 0 && label < V) ? ldv<TIn>(z, label) : 0.f;
+  }
   // pass 1: max + argmax
   float m = -INFINITY;
   int am = 0;
@@ -103,7 +146,14 @@ __global__ __launch_bounds__(1024) void ce_kernel(const TIn* __restrict__ logits
     }
     for (int j = threadIdx.x; j < (int)ld; j += blockDim.x) {
       float g = 0.f;
-      if constexpr (REG) {
+      if constexpr (MIX) {  // on = 1 without REG, off = 0
+        const float lab = (j == label ? on * mr.w : 0.f) + (j == mr.label2 ? on * (1.f - mr.w) : 0.f);
+        if constexpr (REG) {
+          if (j < V && !ignored) g = (__expf(ldv<TIn>(z, j) - m) * inv_s - off - lab) * grad_scale;
+        } else {
+          if (j < V && !ignored) g = (__expf(ldv<TIn>(z, j) - m) * inv_s - lab) * grad_scale;
+        }
+      } else if constexpr (REG) {
         if (j < V && !ignored) g = (__expf(ldv<TIn>(z, j) - m) * inv_s - off - (j == label ? on : 0.f)) * grad_scale;
       } else {
         if (j < V && !ignored) g = (__expf(ldv<TIn>(z, j) - m) * inv_s - (j == label ? 1.f : 0.f)) * grad_scale;
@@ -163,11 +213,12 @@ DPE_DEVICE float* ce_shq() {
 #define DPE_CE_REG_WAVES 4
 #endif
 
-template <typename TIn, typename TOut, int NT, int MAXC, bool REG>
-__global__ __launch_bounds__(NT, NT >= 1024 ? (REG ? DPE_CE_REG_WAVES : 8) : 1) void ce_vec_kernel(const TIn* logits, const int64_t* __restrict__ labels, int V,
+// (the MIX kernels' label pair and weight cost registers: the 1024-thread ones get the REG arm's 128 VGPRs)
+template <typename TIn, typename TOut, int NT, int MAXC, bool REG, bool MIX>
+__global__ __launch_bounds__(NT, NT >= 1024 ? (REG || MIX ? DPE_CE_REG_WAVES : 8) : 1) void ce_vec_kernel(const TIn* logits, const int64_t* __restrict__ labels, int V,
                                                     int64_t ld, float grad_scale, TOut* dlogits,
                                                     float* __restrict__ loss_rows, float* __restrict__ loss_sum,
-                                                    float* __restrict__ correct, int ignore_index, CeReg<REG> ra) {
+                                                    float* __restrict__ correct, int ignore_index, CeReg<REG> ra, CeMix<MIX> mx) {
   constexpr int NW = NT / 64;
   constexpr float L2E = 1.4426950408889634f;
   __shared__ float shm[NW], shs[NW], shz[NW];
@@ -178,6 +229,9 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? (REG ? DPE_CE_REG_WAVES : 8) : 1) 
   const int64_t label = labels[row];
   const bool ignored = (label == ignore_index);
   const int lch = (int)(label >> 3);
+  [[maybe_unused]] CeMixRow<MIX> mr;
+  if constexpr (MIX) mr.init(mx, row, label, ignore_index);
+  [[maybe_unused]] float zy2 = 0.f;  // MIX: z at the second label
   RowChunk<TIn> rc[MAXC];
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
@@ -205,6 +259,13 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? (REG ? DPE_CE_REG_WAVES : 8) : 1) 
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           if (e == (int)(label & 7)) zy = f[e];
+      }
+      if constexpr (MIX) {
+        if (ch == (int)(mr.label2 >> 3)) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (e == (int)(mr.label2 & 7)) zy2 = f[e];
+        }
       }
       float cm = f[0];
       int ce = 0;
@@ -249,6 +310,7 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? (REG ? DPE_CE_REG_WAVES : 8) : 1) 
       }
     }
   }
+  if constexpr (MIX) zy = mr.w * zy + (1.f - mr.w) * zy2;  // this thread's share of zmix (0 for all but the label's owners)
   s = warp_sum(s);
   zy = warp_sum(zy);
   if (lane == 0) { shs[wid] = s; shz[wid] = zy; }
@@ -306,7 +368,17 @@ __global__ __launch_bounds__(NT, NT >= 1024 ? (REG ? DPE_CE_REG_WAVES : 8) : 1) 
         if (ch == lch && !ignored) {
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            if (e == (int)(label & 7)) g[e] -= on;
+            if (e == (int)(label & 7)) {
+              if constexpr (MIX) g[e] -= on * mr.w;
+              else g[e] -= on;
+            }
+        }
+        if constexpr (MIX) {
+          if (ch == (int)(mr.label2 >> 3) && !ignored) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (e == (int)(mr.label2 & 7)) g[e] -= on * (1.f - mr.w);
+          }
         }
         if constexpr (sizeof(TOut) == 2) {
           *(u32x4*)(d + (int64_t)ch * 8) = pack8(g);
@@ -383,16 +455,16 @@ __global__ __launch_bounds__(256) void ce_grad_scale_kernel(const T* __restrict_
   }
 }
 
-template <bool REG, typename TIn, typename TOut>
+template <bool REG, bool MIX, typename TIn, typename TOut>
 bool ce_vec_launch(const TIn* logits, const int64_t* labels, int B, int V, int64_t ld, float gs, TOut* d, float* lr,
-                   float* ls, float* cor, int ign, CeReg<REG> ra, hipStream_t st) {
+                   float* ls, float* cor, int ign, CeReg<REG> ra, CeMix<MIX> mx, hipStream_t st) {
   if (ld % 8) return false;
   const int64_t nch = ld / 8;
 
 #define DPE_CE_VEC(NT, MC)                                                                                         \
   if (nch <= (int64_t)(NT) * (MC)) {                                                                               \
-    hipLaunchKernelGGL((ce_vec_kernel<TIn, TOut, NT, MC, REG>), dim3(B), dim3(NT), 0, st, logits, labels, V, ld, gs, d, \
-                       lr, ls, cor, ign, ra);                                                                 \
+    hipLaunchKernelGGL((ce_vec_kernel<TIn, TOut, NT, MC, REG, MIX>), dim3(B), dim3(NT), 0, st, logits, labels, V, ld, gs, d, \
+                       lr, ls, cor, ign, ra, mx);                                                             \
     return true;                                                                                                   \
   }
   DPE_CE_VEC(64, 1)
@@ -404,7 +476,8 @@ bool ce_vec_launch(const TIn* logits, const int64_t* labels, int B, int V, int64
   DPE_CE_VEC(1024, 4)
   // an fp32 row of 8 chunks per thread is 64 VGPRs of logits alone: the REG arm leaves those rows (more than
   // 32768 fp32 columns) to the three-pass kernel rather than spill
-  if constexpr (!(REG && sizeof(TIn) == 4)) {
+  // (and the MIX arm every row that long: its use is image classification, not the LM head)
+  if constexpr (!(REG && sizeof(TIn) == 4) && !MIX) {
     DPE_CE_VEC(1024, 8)
   }
 #undef DPE_CE_VEC
@@ -416,35 +489,36 @@ bool ce_vec_launch(const TIn* logits, const int64_t* labels, int B, int V, int64
 using namespace dpe;
 
 // one dtype pair: the row-in-registers kernel where the row fits it, else the three-pass one
-template <bool REG, typename TIn, typename TOut>
+template <bool REG, bool MIX, typename TIn, typename TOut>
 static void ce_rows_typed(const TIn* logits, const int64_t* labels, int B, int V, int64_t ld, float grad_scale, TOut* dlogits,
-                          float* loss_rows, float* loss_sum, float* correct, int ignore_index, CeReg<REG> ra,
+                          float* loss_rows, float* loss_sum, float* correct, int ignore_index, CeReg<REG> ra, CeMix<MIX> mx,
                           hipStream_t st) {
-  if (ce_vec_launch<REG>(logits, labels, B, V, ld, grad_scale, dlogits, loss_rows, loss_sum, correct, ignore_index, ra, st))
+  if (ce_vec_launch<REG, MIX>(logits, labels, B, V, ld, grad_scale, dlogits, loss_rows, loss_sum, correct, ignore_index, ra, mx,
+                              st))
     return;
   const int threads = V >= 4096 ? 1024 : 256;
-  hipLaunchKernelGGL((ce_kernel<TIn, TOut, REG>), dim3(B), dim3(threads), 0, st, logits, labels, B, V, ld, grad_scale, dlogits,
-                     loss_rows, loss_sum, correct, ignore_index, ra);
+  hipLaunchKernelGGL((ce_kernel<TIn, TOut, REG, MIX>), dim3(B), dim3(threads), 0, st, logits, labels, B, V, ld, grad_scale, dlogits,
+                     loss_rows, loss_sum, correct, ignore_index, ra, mx);
 }
 
-template <bool REG>
+template <bool REG, bool MIX = false>
 static int dpe_cross_entropy_rows(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld,
                                   float grad_scale, void* dlogits, int out_bf16, float* loss_rows, float* loss_sum,
-                                  float* correct, int ignore_index, CeReg<REG> ra, hipStream_t st) {
+                                  float* correct, int ignore_index, CeReg<REG> ra, hipStream_t st, CeMix<MIX> mx = {}) {
   if (in_bf16) {
     if (out_bf16)
-      ce_rows_typed<REG>((const uint16_t*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct,
-                         ignore_index, ra, st);
+      ce_rows_typed<REG, MIX>((const uint16_t*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, mx, st);
     else
-      ce_rows_typed<REG>((const uint16_t*)logits, labels, B, V, ld, grad_scale, (float*)dlogits, loss_rows, loss_sum, correct,
-                         ignore_index, ra, st);
+      ce_rows_typed<REG, MIX>((const uint16_t*)logits, labels, B, V, ld, grad_scale, (float*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, mx, st);
   } else {
     if (out_bf16)
-      ce_rows_typed<REG>((const float*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct,
-                         ignore_index, ra, st);
+      ce_rows_typed<REG, MIX>((const float*)logits, labels, B, V, ld, grad_scale, (uint16_t*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, mx, st);
     else
-      ce_rows_typed<REG>((const float*)logits, labels, B, V, ld, grad_scale, (float*)dlogits, loss_rows, loss_sum, correct,
-                         ignore_index, ra, st);
+      ce_rows_typed<REG, MIX>((const float*)logits, labels, B, V, ld, grad_scale, (float*)dlogits, loss_rows, loss_sum, correct,
+                         ignore_index, ra, mx, st);
   }
   return 0;
 }
@@ -481,6 +555,23 @@ extern "C" int dpe_cross_entropy_mean_reg(const void* logits, int in_bf16, const
   if (!(eps >= 0.f && eps < 1.f && zl >= 0.f) || V <= 0) return -3;
   const int rc = dpe_cross_entropy_rows<true>(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16, loss_rows, out4,
                                               out4 + 1, ignore_index, CeReg<true>{eps, zl}, st);
+  if (rc == 0) hipLaunchKernelGGL(ce_sum_kernel<true>, dim3(1), dim3(256), 0, st, loss_rows, B, out4, labels, ignore_index);
+  return rc;
+}
+
+// as dpe_cross_entropy_mean_reg with two labels per row (the MIX kernels; eps = zl = 0 takes the ones without REG)
+extern "C" int dpe_cross_entropy_mean_mix(const void* logits, int in_bf16, const int64_t* labels, const int64_t* labels2,
+                                          const float* w, int w_stride, int B, int V, int64_t ld, float grad_scale, void* dlogits,
+                                          int out_bf16, float* loss_rows, float* out4, int ignore_index, float eps, float zl,
+                                          hipStream_t st) {
+  if (dlogits == logits && in_bf16 != out_bf16) return -2;
+  if (!(eps >= 0.f && eps < 1.f && zl >= 0.f) || V <= 0 || !labels2 || !w || (w_stride != 0 && w_stride != 1)) return -3;
+  const CeMix<true> mx{labels2, w, w_stride};
+  const int rc = (eps == 0.f && zl == 0.f)
+                     ? dpe_cross_entropy_rows<false, true>(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16,
+                                                           loss_rows, out4, out4 + 1, ignore_index, CeReg<false>{}, st, mx)
+                     : dpe_cross_entropy_rows<true, true>(logits, in_bf16, labels, B, V, ld, grad_scale, dlogits, out_bf16,
+                                                          loss_rows, out4, out4 + 1, ignore_index, CeReg<true>{eps, zl}, st, mx);
   if (rc == 0) hipLaunchKernelGGL(ce_sum_kernel<true>, dim3(1), dim3(256), 0, st, loss_rows, B, out4, labels, ignore_index);
   return rc;
 }

@@ -657,17 +657,19 @@ class _CEFn(Function):
     clamp / divide / cast kernels at the launch-bound forward -> backward seam."""
 
     @staticmethod
-    def forward(ctx, logits, labels, num_classes: int, ignore_index: int, label_smoothing: float = 0.0, z_loss: float = 0.0):
+    def forward(ctx, logits, labels, num_classes: int, ignore_index: int, label_smoothing: float = 0.0, z_loss: float = 0.0,
+                labels2=None, mix_w=None):
+        mix = {} if labels2 is None else {"labels2": labels2.contiguous(), "mix_w": mix_w}
         out4, d = ext().cross_entropy_mean(logits.contiguous(), labels.contiguous(), num_classes,
                                            logits.dtype == torch.bfloat16, ignore_index,
-                                           label_smoothing=label_smoothing, z_loss=z_loss)
+                                           label_smoothing=label_smoothing, z_loss=z_loss, **mix)
         ctx.save_for_backward(d, out4)
         return out4[2:3].reshape(())
 
     @staticmethod
     def backward(ctx, g):
         d, out4 = ctx.saved_tensors
-        return ext().ce_grad_scale(d, g.float().reshape(1), out4[3:4]), None, None, None, None, None
+        return ext().ce_grad_scale(d, g.float().reshape(1), out4[3:4]), None, None, None, None, None, None, None
 
 
 def _check_ce_reg(label_smoothing: float, z_loss: float):
@@ -687,16 +689,46 @@ def _ce_reference(logits, labels, ignore_index: int, label_smoothing: float, z_l
     return loss
 
 
+def _ce_mix_reference(logits, labels, labels2, mix_w, ignore_index: int, label_smoothing: float, z_loss: float):
+    """The CPU branch with two labels per row: F.cross_entropy on the soft target w onehot(y) + (1 - w) onehot(y2)
+    over the rows whose ``labels`` entry is not ignored (a row whose ``labels2`` entry is ignored has w = 1)."""
+    keep = labels != ignore_index
+    n = keep.sum().clamp(min=1)
+    V = logits.shape[-1]
+    w = mix_w.to(logits.dtype).reshape(-1).expand(labels.numel()) if mix_w.numel() == 1 else mix_w.to(logits.dtype).reshape(-1)
+    w = torch.where(labels2 == ignore_index, torch.ones_like(w), w)
+    y2 = torch.where(labels2 == ignore_index, labels, labels2)
+    tgt = w[:, None] * F.one_hot(labels.clamp(min=0), V) + (1.0 - w)[:, None] * F.one_hot(y2.clamp(min=0), V)
+    rows = F.cross_entropy(logits, tgt.to(logits.dtype), reduction="none", label_smoothing=label_smoothing)
+    if z_loss != 0.0:
+        rows = rows + z_loss * torch.logsumexp(logits, dim=-1).square()
+    return (rows * keep).sum() / n
+
+
 def cross_entropy(logits, labels, num_classes: Optional[int] = None, ignore_index: int = -100,
-                  label_smoothing: float = 0.0, z_loss: float = 0.0):
+                  label_smoothing: float = 0.0, z_loss: float = 0.0, labels2=None, mix_w=None):
     """Mean softmax cross-entropy over rows (torch.nn.CrossEntropyLoss semantics, ``label_smoothing`` included),
-    plus ``z_loss * mean(logsumexp^2)`` over the non-ignored rows."""
+    plus ``z_loss * mean(logsumexp^2)`` over the non-ignored rows.
+
+    ``labels2`` / ``mix_w`` (together; mixup / cutmix targets): a second label per row and the weight ``w`` of the
+    first one, a tensor of one element (the batch's) or one per row -- on the GPU a device fp32 tensor the kernel
+    reads, never a host number.  The row's target is ``w onehot(y) + (1 - w) onehot(y2)``; a row is ignored iff
+    ``labels`` says so, and ``labels2 == ignore_index`` marks a row without partner (``w = 1``)."""
     if num_classes is None:
         num_classes = logits.shape[-1]
     _check_ce_reg(label_smoothing, z_loss)
+    if (labels2 is None) != (mix_w is None):
+        raise ValueError("cross_entropy: labels2 and mix_w go together")
+    if labels2 is not None and not torch.is_tensor(mix_w):
+        raise TypeError("cross_entropy: mix_w must be a tensor (one weight, or one per row)")
     if not logits.is_cuda:
-        return _ce_reference(logits.reshape(-1, logits.shape[-1])[:, :num_classes].float(), labels.reshape(-1),
-                             ignore_index, label_smoothing, z_loss)
+        lf = logits.reshape(-1, logits.shape[-1])[:, :num_classes].float()
+        if labels2 is not None:
+            return _ce_mix_reference(lf, labels.reshape(-1), labels2.reshape(-1), mix_w, ignore_index, label_smoothing, z_loss)
+        return _ce_reference(lf, labels.reshape(-1), ignore_index, label_smoothing, z_loss)
+    if labels2 is not None:
+        return _CEFn.apply(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), num_classes, ignore_index,
+                           float(label_smoothing), float(z_loss), labels2.reshape(-1), mix_w.detach().float())
     return _CEFn.apply(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), num_classes, ignore_index,
                        float(label_smoothing), float(z_loss))
 
@@ -964,6 +996,25 @@ def to_nhwc_input(x: torch.Tensor, cpad: int = 8) -> torch.Tensor:
             y = F.pad(y, (0, cpad - y.shape[-1]))
         return y.contiguous()
     return ext().nchw_to_nhwc(x.float().contiguous(), cpad)
+
+
+MIX_LAYOUTS = {"s2d": 0, "nhwc": 1}
+
+
+def mix_pack(x: torch.Tensor, params: torch.Tensor, layout: str = "s2d", cpad: int = 8) -> torch.Tensor:
+    """``to_s2d_input`` / ``to_nhwc_input`` of the batch mixed with ``x.roll(1, 0)`` by one device row ``params``
+    (``[w_pix, w_lab, x1, y1, x2, y2, mode, lam_raw]``, ``data.BatchMixer.draw``): inside the box the partner's
+    pixel, outside ``w_pix * x + (1 - w_pix) * partner`` in fp32, rounded once to bf16.  One pass over the NCHW fp32
+    batch, GPU only, not differentiable."""
+    if layout not in MIX_LAYOUTS:
+        raise ValueError(f"mix_pack: layout must be one of {sorted(MIX_LAYOUTS)}, got {layout!r}")
+    if x.requires_grad:
+        raise ValueError("mix_pack is not differentiable: the input batch must not require grad")
+    if not x.is_cuda:
+        raise ValueError("mix_pack runs on the GPU (on the CPU BatchMixer mixes with torch ops)")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("mix_pack: x must be an NCHW fp32 batch")
+    return ext().mix_pack(x.contiguous(), params.reshape(8), MIX_LAYOUTS[layout], cpad)
 
 
 # ====================================================== residual-stream linear

@@ -21,7 +21,7 @@ import time
 import torch
 from torch.distributed.elastic.multiprocessing.errors import record
 
-from .data import SyntheticDataset, SyntheticTokens, create_data_loader
+from .data import BatchMixer, SyntheticDataset, SyntheticTokens, create_data_loader
 from .models import get_model
 from .ops import functional as Fx
 from .optim import build_optimizer
@@ -73,6 +73,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "validation loss stays the plain cross-entropy, the logged train loss includes the regularisers")
     p.add_argument("--z-loss", type=float, default=0.0,
                    help="weight of the z-loss (mean logsumexp^2) added to the training loss; validation stays plain")
+    p.add_argument("--mixup-alpha", type=float, default=0.0,
+                   help="mixup: blend every training batch with itself rolled by one, lam ~ Beta(alpha, alpha) drawn on the "
+                        "device per step (0: off); on the GPU the blend happens inside the pass that packs the images and "
+                        "the fused cross-entropy takes both labels; validation stays plain; not for gpt2 models")
+    p.add_argument("--cutmix-alpha", type=float, default=0.0,
+                   help="cutmix: paste torchvision's random box from the rolled batch, area 1 - lam, lam ~ Beta(alpha, alpha) "
+                        "(0: off; image models only)")
+    p.add_argument("--mix-prob", type=float, default=None,
+                   help="with --mixup-alpha / --cutmix-alpha: the probability of mixing a batch at all (default 1)")
+    p.add_argument("--mix-switch-prob", type=float, default=None,
+                   help="with both alphas: the probability of cutmix over mixup (default 0.5)")
     p.add_argument("--dropout", type=float, default=0.0,
                    help="gpt2 models: dropout rate in [0, 1) on the embedding sum, the attention probabilities (inside "
                         "the flash kernels, at the 8-bit rate round(256 p) / 256) and both residual branches; training "
@@ -134,10 +145,11 @@ def _datasets(args, device):
 
 
 def train_epoch(model, loader, optimizer, criterion, device, epoch, rank, grad_accum=1, max_steps=None, watchdog=None,
-                fused_loss=False):
+                fused_loss=False, mixer=None):
     """Reference `train_epoch` (`train.py:119-151`); loss accumulated on device.  ``fused_loss``: the
     model takes the targets and returns the loss itself (GPT-2's fused LM head + CE, reference
-    `train.py:136-137` as one op: the [B, T, V] logits never materialise)."""
+    `train.py:136-137` as one op: the [B, T, V] logits never materialise).  ``mixer`` (a ``BatchMixer``): every batch
+    is mixed once it is on the device and ``criterion`` gets the target triple ``(y, y2, w)``."""
     model.train()
     total_loss = torch.zeros((), dtype=torch.float64, device=device)
     num_batches = 0
@@ -151,6 +163,8 @@ def train_epoch(model, loader, optimizer, criterion, device, epoch, rank, grad_a
         fault.maybe_inject(epoch, batch_idx)
         data, target = data.to(device, non_blocking=True), target.to(device, non_blocking=True)
         doc = [d.to(device, non_blocking=True) for d in doc]
+        if mixer is not None:
+            data, target = mixer(data, target, **_mix_layout(model))
         sync = (batch_idx + 1) % grad_accum == 0 or batch_idx + 1 == n_eff
         ctx = model.no_sync() if (not sync and hasattr(model, "no_sync")) else _null()
         with ctx:
@@ -173,6 +187,14 @@ def train_epoch(model, loader, optimizer, criterion, device, epoch, rank, grad_a
         if batch_idx % 10 == 0 and rank == 0:
             logger.info(f"Epoch {epoch}, Batch {batch_idx}/{nb}, Loss: {loss.item():.4f}")
     return (total_loss / max(1, num_batches)).item()
+
+
+def _mix_layout(model) -> dict:
+    """The packed form the model's stem takes (``BatchMixer.__call__``): ResNet's space-to-depth stem or its NHWC one."""
+    m = getattr(model, "module", model)
+    if getattr(m, "s2d_stem", True):
+        return {"layout": "s2d"}
+    return {"layout": "nhwc", "cpad": getattr(m, "in_pad", 8)}
 
 
 @torch.no_grad()
@@ -270,6 +292,21 @@ def main(argv=None):
         parser.error("--ema-decay must be in [0, 1)")
     if args.dropout > 0.0 and not args.model.startswith("gpt2"):
         parser.error("--dropout needs a gpt2 model")
+    if not args.mixup_alpha >= 0.0:
+        parser.error("--mixup-alpha must be >= 0")
+    if not args.cutmix_alpha >= 0.0:
+        parser.error("--cutmix-alpha must be >= 0")
+    mixing = args.mixup_alpha > 0.0 or args.cutmix_alpha > 0.0
+    for flag, v in (("--mix-prob", args.mix_prob), ("--mix-switch-prob", args.mix_switch_prob)):
+        if v is not None and not mixing:
+            parser.error(f"{flag} needs --mixup-alpha or --cutmix-alpha")
+        if v is not None and not 0.0 <= v <= 1.0:
+            parser.error(f"{flag} must be in [0, 1]")
+    if args.model.startswith("gpt2") and (mixing or args.mix_prob is not None or args.mix_switch_prob is not None):
+        parser.error("--mixup-alpha / --cutmix-alpha / --mix-prob / --mix-switch-prob are for the image and feature "
+                     "models, not gpt2")
+    if args.cutmix_alpha > 0.0 and not args.model.startswith("resnet"):
+        parser.error("--cutmix-alpha needs an image model (resnet50, resnet_tiny)")
     ensure_single_process_env()
     rank, world_size, local_rank = pdist.init_process_group(args.backend, comm_max_channels=args.comm_max_channels)
     logger.info(f"Initialized process group: rank={rank}, world_size={world_size}, local_rank={local_rank}")
@@ -308,7 +345,15 @@ def main(argv=None):
                                    if opt_name == "muon" else {}))
 
     def criterion(out, tgt):  # training only: validate() takes Fx.cross_entropy_eval, the plain cross-entropy
+        if isinstance(tgt, tuple):  # a BatchMixer's (y, y2, w)
+            return Fx.cross_entropy(out, tgt[0], num_classes, label_smoothing=args.label_smoothing, z_loss=args.z_loss,
+                                    labels2=tgt[1], mix_w=tgt[2])
         return Fx.cross_entropy(out, tgt, num_classes, label_smoothing=args.label_smoothing, z_loss=args.z_loss)
+
+    mixer = None
+    if mixing:
+        mixer = BatchMixer(args.mixup_alpha, args.cutmix_alpha, 1.0 if args.mix_prob is None else args.mix_prob,
+                           0.5 if args.mix_switch_prob is None else args.mix_switch_prob, device=device)
 
     start_epoch = 0
     if rank == 0:
@@ -329,7 +374,7 @@ def main(argv=None):
         epoch_start = time.time()
         train_sampler.set_epoch(epoch)
         train_loss = train_epoch(model, train_loader, optimizer, criterion, device, epoch, rank, args.grad_accum,
-                                 args.max_steps, watchdog, fused_loss=args.model.startswith("gpt2"))
+                                 args.max_steps, watchdog, fused_loss=args.model.startswith("gpt2"), mixer=mixer)
         val_loss, val_accuracy = validate(model, val_loader, criterion, device, num_classes, args.max_steps, watchdog)
 
         metrics = torch.tensor([train_loss, val_loss, val_accuracy], device=device)
