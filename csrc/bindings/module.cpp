@@ -14,6 +14,7 @@ PYBIND11_MODULE(_C, m) {
   dpe_ops::register_conv(m);
   dpe_ops::register_bn(m);
   dpe_ops::register_ops(m);
+  dpe_ops::register_decode(m);
   dpe_gemm::register_gemm(m);
   dpe::register_comm(m);
 }

@@ -69,4 +69,5 @@ bool hgemm_conv_wgrad_on();  // DPE_HGEMM_CONV_WGRAD
 void register_conv(pybind11::module& m);  // conv.cpp
 void register_bn(pybind11::module& m);    // bn.cpp
 void register_ops(pybind11::module& m);   // ops.cpp
+void register_decode(pybind11::module& m);  // decode.cpp
 }  // namespace dpe_ops

@@ -174,6 +174,25 @@ int dpe_attn_fwd_drop(const uint16_t* qkv, uint16_t* out, float* lse, int B, int
 int dpe_attn_bwd_drop(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                       uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, const int32_t* doc_start,
                       const int32_t* doc_end, const int64_t* rng, uint32_t stream, uint32_t thr, hipStream_t st);
+// ---- decode.hip
+// one query per (b, h) against the head-major cache kc / vc [B, H, Tmax, 64]; qkv_step [B, 3, H, 64]; len int32 [B]
+// (clamped into [0, Tmax - 1]); S key splits (ws: dpe_attn_decode_ws_floats fp32, unused for S = 1); out [B, H * 64]
+int dpe_attn_decode_splits(int BH, int Tmax);  // the default S: a function of the launch shape only
+int64_t dpe_attn_decode_ws_floats(int BH, int S);
+int dpe_attn_decode(const uint16_t* qkv_step, uint16_t* kc, uint16_t* vc, const int32_t* len, int B, int H, int Tmax, int S,
+                    float scale, float* ws, uint16_t* out, hipStream_t st);
+// y[M, N] = x[M, K] w[N, K]^T, M <= 16, K % 32 == 0, N % 16 == 0, row strides % 8 == 0.  bf16 out (+ bias, GELU) or
+// fp32 out (+ bias, + fp32 residual that may alias y).  ksplit > 1: ws of ksplit * M * N floats.
+int dpe_linear_skinny_ok(int M, int N, int K, int64_t ldx, int64_t ldw);
+int dpe_linear_skinny_ksplit(int M, int N, int K);  // the default K split over blocks
+int dpe_linear_skinny_waves();                      // K partials summed inside a block
+int dpe_linear_skinny(const uint16_t* x, int64_t ldx, const uint16_t* w, int64_t ldw, int M, int N, int K, const float* bias,
+                      int gelu, int out_f32, const float* res, int64_t ldr, void* y, int64_t ldy, int ksplit, float* ws,
+                      hipStream_t st);
+// one token per row: temperature (0 = argmax), top_k (0 = off), top_p (1 = off), Gumbel-max from rng = device
+// int64[2] (seed, offset); done int32 [B] or null; eos_id -1 = none
+int dpe_sample_logits(const void* logits, int in_bf16, int B, int V, int64_t ld, float temperature, int top_k, float top_p,
+                      const int64_t* rng, uint32_t stream, int eos_id, int32_t* done, int64_t* out, hipStream_t st);
 // ---- gemm_f32.hip
 int dpe_gemm_f32(const float* A, const float* B, float* C, int64_t sam, int64_t sak, int64_t sbk, int64_t sbn,
                  int64_t ldc, int M, int N, int K, const float* bias, float alpha, int relu, float drop_p,

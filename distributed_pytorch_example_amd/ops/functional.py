@@ -1145,3 +1145,153 @@ def lm_head(x, wte, vocab_pad_to: int = 64):
     if not x.is_cuda:
         return F.linear(x.float(), wte)
     return _LMHeadFn.apply(x, wte, Vp - V)
+
+
+# =============================================================== generation
+# One decode step streams every weight and the KV cache once per token; its kernels (csrc/kernels/decode.hip) share
+# nothing with the training tiles.  Each wrapper has a torch path for the CPU with the same semantics.
+SKINNY_MAX_M = 16
+# (N, K) -> the smallest M from which scripts/bench_decode.py measured Fx.linear faster than linear_skinny
+# (docs/perf_notes.md, "GPT-2 decoding": GPT-2-small's five projection shapes at M = 1, 8, 16; only the LM head at
+# M = 16 lost, by 4 %).  A shape that has not been measured runs on the skinny kernel: that default is an assumption
+# from the byte count, not a measurement.
+SKINNY_SLOWER: dict = {(50304, 768): 16}
+
+
+def attn_decode(qkv_step, kc, vc, lens, n_head: int, scale: Optional[float] = None, splits: int = 0):
+    """One query per (row, head) against the cache.  qkv_step [B, 3 * H * 64] (the new token's c_attn output),
+    kc / vc [B, H, Tmax, 64], lens int32 [B] = tokens already cached per row (clamped into [0, Tmax - 1]).  Row b
+    attends keys 0 .. lens[b]; key lens[b] is the step's own K/V, which is also stored into the cache at that
+    index.  Returns [B, H * 64].  ``splits``: the number of key splits (0: a function of the launch shape)."""
+    B = qkv_step.shape[0]
+    D = qkv_step.numel() // (B * 3 * n_head)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if qkv_step.is_cuda:
+        if D != 64:
+            raise ValueError("attn_decode: the kernel takes head dim 64")
+        return ext().attn_decode(qkv_step.reshape(B, 3, n_head, D), kc, vc, lens, float(scale), int(splits))
+    Tmax = kc.shape[2]
+    q, k, v = qkv_step.reshape(B, 3, n_head, D).to(kc.dtype).unbind(1)  # [B, H, D]
+    L = lens.long().clamp(0, Tmax - 1)
+    rows = torch.arange(B)
+    kc[rows, :, L] = k
+    vc[rows, :, L] = v
+    seen = (torch.arange(Tmax)[None, :] <= L[:, None])[:, None, :]  # [B, 1, Tmax]
+    s = torch.einsum("bhd,bhtd->bht", q.float(), kc.float()) * scale
+    p = torch.softmax(torch.where(seen, s, torch.full_like(s, float("-inf"))), dim=-1)
+    o = torch.einsum("bht,bhtd->bhd", p, torch.where(seen.unsqueeze(-1), vc.float(), torch.zeros((), dtype=torch.float32)))
+    return o.reshape(B, n_head * D)
+
+
+def linear_skinny(x, weight, bias=None, act: int = ACT_NONE, residual=None, out_f32: bool = False, pad_rows: int = 0,
+                  ksplit: int = 0):
+    """``linear`` / ``linear_residual`` for M <= 16 rows, no autograd: x [M, K] bf16 against the bf16 shadow of
+    ``weight`` [N, K] (``pad_rows`` zero rows appended, the LM head's padding).  bf16 out with optional bias and
+    GELU, or -- ``out_f32`` / ``residual`` -- fp32 out with optional bias and the fp32 residual, which is updated
+    in place.  Shapes outside the kernel's envelope (M <= 16, K % 32 == 0, N % 16 == 0) or listed in SKINNY_SLOWER
+    run on Fx.linear / Fx.linear_residual."""
+    if act not in (ACT_NONE, ACT_GELU):
+        raise ValueError("linear_skinny: act must be ACT_NONE or ACT_GELU")
+    out_f32 = out_f32 or residual is not None
+    if out_f32 and act != ACT_NONE:
+        raise ValueError("linear_skinny: GELU goes with the bf16 output")
+    with torch.no_grad():
+        if not x.is_cuda:
+            w = F.pad(weight, (0, 0, 0, pad_rows)) if pad_rows else weight
+            if residual is not None:
+                return residual.add_(F.linear(x.float(), w, bias))
+            return linear(x, w, bias, act, out_f32)
+        M, K = x.shape
+        N = weight.shape[0] + pad_rows
+        xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+        C = ext()
+        if M >= SKINNY_SLOWER.get((N, K), SKINNY_MAX_M + 1) or not C.linear_skinny_ok(M, N, K, xb.stride(0) if M > 1 else K, K):
+            if residual is not None:
+                return linear_residual(xb, weight, bias, residual) if pad_rows == 0 else residual.add_(
+                    _LinearFn.apply(xb, weight, bias, ACT_NONE, True))
+            if pad_rows:
+                assert bias is None and act == ACT_NONE, "a padded weight is the LM head"
+                y = _LMHeadFn.apply(xb, weight, pad_rows)
+                return y.float() if out_f32 else y
+            return linear(xb, weight, bias, act, out_f32)
+        return C.linear_skinny(xb, shadow(weight, pad_rows), bias.detach() if bias is not None else None, act == ACT_GELU,
+                               out_f32, residual, residual, int(ksplit))
+
+
+_sampler_states: dict = {}
+
+
+def sampler_state(device) -> DropoutState:
+    """The sampler's own device RNG state (seed, offset) of ``device``: a DropoutState apart from the dropout one,
+    so generating between two training steps does not move the dropout masks."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    st = _sampler_states.get(device)
+    if st is None:
+        st = _sampler_states[device] = DropoutState(device)
+    return st
+
+
+def sample_keep(logits, temperature: float, top_k: int = 0, top_p: float = 1.0):
+    """(s, keep) of the sampler's filters in torch ops: s = logits / temperature in fp32 and the bool mask of the
+    columns that stay.  Defined on values: top-k keeps s >= the k-th largest value (ties stay); top-p then keeps j iff
+    the softmax mass, over what top-k kept, of the strictly larger values is < top_p."""
+    s = logits.float() / temperature
+    V = s.shape[-1]
+    keep = torch.ones_like(s, dtype=torch.bool)
+    if 0 < top_k < V:
+        keep = s >= torch.topk(s, top_k, dim=-1).values[..., -1:]
+    if top_p < 1.0:
+        sm = torch.where(keep, s, torch.full_like(s, float("-inf")))
+        sv, order = torch.sort(sm, dim=-1, descending=True)
+        pr = torch.softmax(sv, dim=-1)
+        above = torch.cumsum(pr, dim=-1) - pr  # mass of the earlier entries; equal values share their group's first
+        i = torch.arange(V, device=s.device).expand_as(sv)
+        first = torch.cummax(torch.where(torch.cat([torch.ones_like(sv[..., :1], dtype=torch.bool),
+                                                    sv[..., 1:] != sv[..., :-1]], dim=-1), i, torch.zeros_like(i)), dim=-1).values
+        kept_sorted = torch.gather(above, -1, first) < top_p
+        keep = keep & torch.zeros_like(keep).scatter(-1, order, kept_sorted)
+    return s, keep
+
+
+def sample_logits(logits, V: Optional[int] = None, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, state=None,
+                  eos_id: Optional[int] = None, done=None, generator=None, stream: int = 0):
+    """One token per row of ``logits`` [B, ld] (bf16 or fp32; only the first ``V`` columns are candidates) -> int64
+    [B].  temperature 0: the argmax, lowest index on ties.  Otherwise s = z / temperature, the filters of
+    ``sample_keep`` and the arg max over the kept columns of s + Gumbel noise, lowest index on ties.  On the GPU the
+    noise is Philox from ``state`` (a DropoutState, default ``sampler_state``), which is advanced by B * ceil(V / 4);
+    on the CPU it is drawn from torch's ``generator``.  ``done`` (int32 [B]) with ``eos_id``: a row whose flag is set
+    emits eos_id, a row that draws eos_id sets its flag."""
+    B, ld = logits.shape
+    V = ld if V is None else int(V)
+    if not 1 <= V <= ld:
+        raise ValueError(f"sample_logits: V = {V} outside the {ld} columns")
+    if not (temperature >= 0.0 and top_k >= 0 and 0.0 < top_p <= 1.0):
+        raise ValueError("sample_logits: need temperature >= 0, top_k >= 0 and 0 < top_p <= 1")
+    eos = -1 if eos_id is None else int(eos_id)
+    if logits.is_cuda:
+        if logits.dtype not in (torch.bfloat16, torch.float32):
+            logits = logits.float()
+        Vp = (V + 7) // 8 * 8
+        if logits.stride(1) != 1 or (B > 1 and logits.stride(0) % 8) or ld < Vp or logits.data_ptr() % 16:
+            logits = F.pad(logits[:, :V], (0, Vp - V))
+        if state is None:
+            state = sampler_state(logits.device)
+        tok = ext().sample_logits(logits, V, float(temperature), int(top_k), float(top_p), state.tensor(), int(stream), eos, done)
+        state.advance(B * ((V + 3) // 4))
+        return tok
+    z = logits[:, :V].float()
+    col = torch.arange(V).expand(B, V)
+    if temperature == 0.0:
+        score = z
+    else:
+        s, keep = sample_keep(z, temperature, top_k, top_p)
+        u = torch.rand(B, V, generator=generator).clamp_(min=2.0 ** -24, max=1.0 - 2.0 ** -24)
+        score = torch.where(keep, s - torch.log(-torch.log(u)), torch.full_like(s, float("-inf")))
+    tok = torch.where(score == score.max(dim=-1, keepdim=True).values, col, torch.full_like(col, V)).min(dim=-1).values
+    if done is not None and eos >= 0:
+        tok = torch.where(done != 0, torch.full_like(tok, eos), tok)
+        done |= (tok == eos).to(done.dtype)
+    return tok
