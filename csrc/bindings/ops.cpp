@@ -205,6 +205,16 @@ Tensor nchw_to_nhwc(const Tensor& x, int64_t cpad) {
   return y;
 }
 
+Tensor patchify(const Tensor& x, int64_t p) {
+  CHECK_GPU(x); CHECK_F32(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.dim() == 4, "patchify: x must be [N,C,H,W]");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(p >= 8 && p % 8 == 0 && H % p == 0 && W % p == 0, "patchify: patch must be a multiple of 8 that divides H and W");
+  Tensor y = at::empty({N, (H / p) * (W / p), C * p * p}, x.options().dtype(at::kBFloat16));
+  CHECK_RC(dpe_patchify(fp(x), bpm(y), (int)N, (int)C, (int)H, (int)W, (int)p, cur_stream()), "patchify");
+  return y;
+}
+
 Tensor nchw_to_s2d(const Tensor& x) {
   CHECK_GPU(x); CHECK_F32(x); CHECK_CONTIG(x);
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
@@ -577,10 +587,18 @@ const int64_t* drop_rng(double p, const c10::optional<Tensor>& rng, int64_t stre
   return (const int64_t*)rng->data_ptr();
 }
 
+// causal = false: bidirectional attention over the first seq_len rows (0 = T); no doc_start, no dropout.
+void bidir_args(const c10::optional<Tensor>& doc_start, const c10::optional<Tensor>& doc_end, double dropout_p,
+                const c10::optional<Tensor>& rng, int64_t seq_len, int64_t T) {
+  TORCH_CHECK(!has(doc_start) && !has(doc_end), "attn: causal=False takes no doc_start / doc_end");
+  TORCH_CHECK(dropout_p == 0.0 && !has(rng), "attn: causal=False takes no dropout arguments");
+  TORCH_CHECK(seq_len >= 0 && seq_len <= T, "attn: seq_len must be in [1, T] (0 = T), got ", seq_len);
+}
+
 std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal, const c10::optional<Tensor>& out_,
                              const c10::optional<Tensor>& lse_, const c10::optional<Tensor>& doc_start,
                              const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng,
-                             int64_t stream) {
+                             int64_t stream, int64_t seq_len) {
   CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_CONTIG(qkv);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   TORCH_CHECK(qkv.numel() == B * T * 3 * H * D, "attn: qkv must be [B,T,3,H,D]");
@@ -590,6 +608,14 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool ca
   CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out); CHECK_GPU(lse); CHECK_F32(lse); CHECK_CONTIG(lse);
   TORCH_CHECK(out.numel() == B * T * H * D && lse.numel() == B * H * T, "attn_fwd: out is [B,T,H,D], lse [B,H,T]");
   TORCH_CHECK(has(doc_start) == has(doc_end), "attn_fwd: doc_start and doc_end go together");
+  if (!causal) {
+    bidir_args(doc_start, doc_end, dropout_p, rng, seq_len, T);
+    CHECK_RC(dpe_attn_fwd_bidir(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale,
+                                (int)(seq_len ? seq_len : T), cur_stream()),
+             "attn_fwd (bidirectional: LDS-DMA kernels only)");
+    return {out, lse};
+  }
+  TORCH_CHECK(seq_len == 0, "attn: seq_len goes with causal=False");
   uint32_t thr;
   if (const int64_t* rp = drop_rng(dropout_p, rng, stream, qkv, &thr)) {
     CHECK_RC(dpe_attn_fwd_drop(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal,
@@ -607,7 +633,8 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool ca
 
 Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const Tensor& lse, int64_t H, double scale,
                 bool causal, const c10::optional<Tensor>& dqkv_, const c10::optional<Tensor>& doc_start,
-                const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng, int64_t stream) {
+                const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng, int64_t stream,
+                int64_t seq_len) {
   CHECK_GPU(qkv); CHECK_BF16(dout); CHECK_CONTIG(dout); CHECK_CONTIG(out);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   Tensor dqkv = has(dqkv_) ? *dqkv_ : at::empty_like(qkv);
@@ -615,6 +642,14 @@ Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const 
   TORCH_CHECK(dqkv.numel() == qkv.numel(), "attn_bwd: dqkv must have qkv's size");
   Tensor delta = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
   TORCH_CHECK(has(doc_start) == has(doc_end), "attn_bwd: doc_start and doc_end go together");
+  if (!causal) {
+    bidir_args(doc_start, doc_end, dropout_p, rng, seq_len, T);
+    CHECK_RC(dpe_attn_bwd_bidir(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
+                                (float)scale, (int)(seq_len ? seq_len : T), cur_stream()),
+             "attn_bwd (bidirectional: LDS-DMA kernels only)");
+    return dqkv;
+  }
+  TORCH_CHECK(seq_len == 0, "attn: seq_len goes with causal=False");
   uint32_t thr;
   if (const int64_t* rp = drop_rng(dropout_p, rng, stream, qkv, &thr)) {
     CHECK_RC(dpe_attn_bwd_drop(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
@@ -654,6 +689,8 @@ void register_ops(pybind11::module& m) {
   m.def("colsum", &colsum, py::arg("dy"), py::arg("db"), py::arg("accumulate") = false);
   m.def("nchw_to_s2d", &nchw_to_s2d, py::arg("x"));
   m.def("nchw_to_nhwc", &nchw_to_nhwc, py::arg("x"), py::arg("cpad") = 8);
+  m.def("patchify", &patchify, py::arg("x"), py::arg("patch"),
+        "fp32 NCHW -> bf16 [N, (H/p)(W/p), C p p] patch rows ordered (c, py, px)");
   m.def("embedding_fwd", &embedding_fwd, py::arg("idx"), py::arg("wte"), py::arg("wpe") = py::none(),
         py::arg("pos") = py::none());
   m.def("embedding_bwd", &embedding_bwd, py::arg("idx"), py::arg("dout"), py::arg("dwte"), py::arg("dwpe") = py::none(),
@@ -707,10 +744,12 @@ void register_ops(pybind11::module& m) {
         }, py::arg("stop"), py::arg("value") = 1, "set a cu_hog stop flag, ordered on the current stream");
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("causal") = true,
         py::arg("out") = py::none(), py::arg("lse") = py::none(), py::arg("doc_start") = py::none(),
-        py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0);
+        py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0,
+        py::arg("seq_len") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("H"),
         py::arg("scale"), py::arg("causal") = true, py::arg("dqkv") = py::none(), py::arg("doc_start") = py::none(),
-        py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0);
+        py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0,
+        py::arg("seq_len") = 0);
   m.def("dropout_add", &dropout_add, py::arg("res"), py::arg("y"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,
         py::arg("out") = py::none(), "fp32 res + dropout(y) (y bf16 or fp32); mask from the device rng state int64[2] (seed, offset) and the stream");
   m.def("dropout_cast", &dropout_cast, py::arg("g"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,

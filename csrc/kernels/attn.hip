@@ -35,6 +35,8 @@
 //   ~1.3 TB/s atomic rate: ~210 MB per layer).
 // Packed documents (doc_start / doc_end, block-diagonal causal mask): PACKED instantiations of the three LDS-DMA
 //   kernels, described at each; the causal instantiations compile to what they were without the template.
+// Bidirectional attention with a key-length bound (ViT: no causal mask, L of the T rows are real): BIDIR instantiations
+//   of the same three kernels, described at each; every other instantiation compiles to what it was.
 #include <type_traits>
 
 #include "common.h"
@@ -368,10 +370,19 @@ DPE_DEVICE bool drop_keep(uint32_t word, int byte, uint32_t thr) { return ((word
 // doc_start only choose tiles (clamped to the causal kernel's walk) and masks, never an address.
 // DROP: dropout on P.  The row sum (and lse2) take the undropped bf16 P, O accumulates the dropped fragments and the
 // 256 / (256 - thr) scale is folded into the final 1 / l; a dropped or masked P is an exact 0 by select.
-template <bool PACKED, bool DROP>
+// BIDIR (no causal mask, a key-length bound; no PACKED, no DROP): rows >= L of a sequence are padding.  Query i < L sees
+// the keys 0 <= j < L, so every live wave walks the key tiles 0 .. ceil(L / 64) - 1: the full ones on the mask-free
+// path, the last one (L % 64 != 0) on a path with the upper bound j < L -- a masked key is left out of the row max and
+// its P is an exact 0 by select after the exp2, so the padding rows of K and V (finite) reach no output bit.  The
+// tail tile's first key is visible to every query, so no row meets a fully masked tile and MK == 2's -inf cases are not
+// needed.  A workgroup past L stores zeros and leaves; a wave past L only stages its DMA pieces and stores zeros; a
+// wave that straddles L computes all 32 rows and selects zeros at the store.  out rows >= L are exact zeros and
+// lse2 rows >= L are 0.0f.  L chooses loop bounds and masks only, never an address.
+template <bool PACKED, bool DROP, bool BIDIR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_fwd_dma_kernel(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse2, int B, int T, int H,
-    float sl2, const int* __restrict__ doc_start, AttnDrop dr) {
+    float sl2, const int* __restrict__ doc_start, AttnDrop dr, int L) {
+  static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
   constexpr int KB = 2 * AKV * 64, STG = KB + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
@@ -384,7 +395,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
   const int q0w = qt * FQ + 32 * w;
   const bool live = q0w < T;
   const int ktw = live ? (q0w + 31) / AKV : -1;
-  const int nkt = min((qt * FQ + FQ - 1) / AKV, T / AKV - 1) + 1;
+  const int nkt = BIDIR ? (L + AKV - 1) / AKV : min((qt * FQ + FQ - 1) / AKV, T / AKV - 1) + 1;
   // packed: first key tile of the workgroup / of the wave, first key no lower mask is needed from, the lane's bounds
   int kt0 = 0, klo = 0, dshi = 0, ds[2] = {0, 0};
   if constexpr (PACKED) {
@@ -395,6 +406,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
       dshi = __builtin_amdgcn_readfirstlane(dsb[q0w + 31]);
       ds[0] = dsb[q0w + li];
       ds[1] = dsb[q0w + 16 + li];
+    }
+  }
+  if constexpr (BIDIR) {
+    if (qt * FQ >= L) {  // every query of the workgroup is padding (workgroup-uniform: no barrier is left behind)
+      if (live) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int myq = q0w + 16 * r + li;
+          uint16_t* o = out + ((int64_t)(b * T + myq) * H + h) * AD;
+#pragma unroll
+          for (int d = 0; d < 4; ++d) *(u32x2*)(o + 16 * d + 4 * g) = u32x2{0u, 0u};
+          if (g == 0) lse2[(int64_t)bh * T + myq] = 0.f;
+        }
+      }
+      return;
     }
   }
 
@@ -443,7 +469,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
   float m[2] = {-INFINITY, -INFINITY};
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});
-  const int kd = (q0w + 1) / AKV;
+  // bidirectional: the key tiles below kd are full.  kd is then workgroup-uniform; the empty asm keeps it in a VGPR so the
+  // choice between the two compute paths stays a per-wave (exec) branch as in the causal kernel -- as scalar control flow
+  // the compiler hoists across both paths and spills 36 registers under the 168-VGPR cap
+  int kd = BIDIR ? L / AKV : (q0w + 1) / AKV;
+  if constexpr (BIDIR) asm volatile("" : "+v"(kd));
   // dropout: the counter of the granule this lane draws (key group nt = li & 3) in key tile 0, per row block
   [[maybe_unused]] uint64_t dseed = 0, dctr[2] = {0, 0};
   if constexpr (DROP) {
@@ -454,7 +484,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
       dctr[r] = (uint64_t)dr.rng[1] + ((uint64_t)bh * n4 + (uint64_t)((q0w + 16 * r + li) >> 2)) * n4 + (uint64_t)(4 * (li & 3) + g);
   }
 
-  // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask
+  // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask, 3 (bidirectional only) key < L
   auto compute = [&](int kt, const char* s, auto maskc) __attribute__((always_inline)) {
     constexpr int MK = decltype(maskc)::value;
     constexpr bool MASK = MK == 1;
@@ -488,6 +518,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
         mx = rowmax4(mx);
         mc[r] = mx == -INFINITY ? mx : mx * sl2;
         need[r] = mc[r] > (m[r] == -INFINITY ? m[r] : m[r] + RESCALE_TH);  // false for a row without a visible key
+      } else if constexpr (MK == 3) {  // the row max over the keys < L; the tile's first key is one, so it is finite
+        const int hi = L - kt * AKV - 4 * g;
+        mx = -INFINITY;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) mx = (16 * nt + e < hi) ? fmaxf(mx, sc[r][nt][e]) : mx;
+        mc[r] = rowmax4(mx) * sl2;
+        need[r] = mc[r] > m[r] + RESCALE_TH;
       } else {
         mx = sc[r][0][0];
 #pragma unroll
@@ -524,6 +563,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
           for (int e = 0; e < 4; ++e) {
             const float pv = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
             sc[r][nt][e] = ((16 * nt + e <= lim) & (16 * nt + e >= lo)) ? pv : 0.f;
+          }
+      } else if constexpr (MK == 3) {  // a masked P is 0 by select after the exp2 (which may have overflowed)
+        const float nm = -m[r];
+        const int hi = L - kt * AKV - 4 * g;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float pv = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
+            sc[r][nt][e] = (16 * nt + e < hi) ? pv : 0.f;
           }
       } else {
         const float nm = -m[r];
@@ -568,6 +617,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
         else if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
         else compute(kt, smem + cur * STG, std::integral_constant<int, 1>{});
       }
+    } else if constexpr (BIDIR) {
+      if (q0w < L) {  // a wave past L only stages its pieces of the tiles
+        if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
+        else compute(kt, smem + cur * STG, std::integral_constant<int, 3>{});
+      }
     } else {
       if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
       else if (kt <= ktw) compute(kt, smem + cur * STG, std::integral_constant<int, 1>{});
@@ -591,9 +645,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
       u32x2 pk2;
       pk2[0] = pack_bf2(acc[r][d][0] * inv, acc[r][d][1] * inv);
       pk2[1] = pack_bf2(acc[r][d][2] * inv, acc[r][d][3] * inv);
+      if constexpr (BIDIR) pk2 = myq < L ? pk2 : u32x2{0u, 0u};
       *(u32x2*)(o + 16 * d + 4 * g) = pk2;
     }
-    if (g == 0) lse2[(int64_t)bh * T + myq] = m[r] + __log2f(l);
+    float ls = m[r] + __log2f(l);
+    if constexpr (BIDIR) ls = myq < L ? ls : 0.f;
+    if (g == 0) lse2[(int64_t)bh * T + myq] = ls;
   }
 }
 
@@ -777,12 +834,16 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
 // DROP: P is dropped for dV (the 256 / (256 - thr) scale goes into the final dV), and dS = P (M s dP - delta): the dP
 // chain starts from 0, not -delta, because the mask multiplies dP before the subtraction.  The DROP instantiations need
 // ~300 VGPRs (the mask words and -delta live beside P and dP): one wave per SIMD, no scratch; capped at 256 they spill.
-template <bool PACKED, bool DROP>
+// BIDIR: the query-tile loop runs over the tiles 0 .. ceil(L / 64) - 1 for every key; the last one (L % 64 != 0) selects
+// P and dS of the queries >= L to 0 after the exp2.  A workgroup past L stores zeros and leaves, a wave past L only
+// stages, a wave that straddles L selects zeros at the store: dK / dV rows >= L are exact zeros.
+template <bool PACKED, bool DROP, bool BIDIR = false>
 __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
                                                        const float* __restrict__ lse2, const float* __restrict__ delta,
                                                        uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
                                                        float scale, const int* __restrict__ doc_start,
-                                                       const int* __restrict__ doc_end, AttnDrop dr) {
+                                                       const int* __restrict__ doc_end, AttnDrop dr, int L) {
+  static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
   // per buffer: Qk Qm dOk dOm (8 KB each) + lse, delta (512 B) (+ packed: doc_start, 256 B)
   constexpr int BUF = 4 * 8192 + 512 + (PACKED ? 256 : 0);
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -799,6 +860,22 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
   const int k0w = kt * BKW + 32 * w;  // the wave's first key
   const bool live = k0w < T;
   const int qtw = k0w / AQ;           // first query tile that reaches the wave's keys
+  if constexpr (BIDIR) {
+    if (kt * BKW >= L) {  // every key of the workgroup is padding (workgroup-uniform: no barrier is left behind)
+      if (live) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          uint16_t* dkb = dqkv + (int64_t)b * T * RS + (int64_t)(k0w + 16 * r + li) * RS + H * AD + (int64_t)h * AD;
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            *(u32x2*)(dkb + 16 * d + 4 * g) = u32x2{0u, 0u};
+            *(u32x2*)(dkb + H * AD + 16 * d + 4 * g) = u32x2{0u, 0u};
+          }
+        }
+      }
+      return;
+    }
+  }
 
   // wave's own 32 keys as B operands (key on lane)
   bf16x8 kf[2][2], vf[2][2];
@@ -858,9 +935,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
     if constexpr (PACKED)
       if (tid >= 128 && tid < 192) ((int*)(smem + buf * BUF + 4 * 8192 + 512))[tid - 128] = dsv;
   };
-  const int qs = (kt * BKW) / AQ;
+  const int qs = BIDIR ? 0 : (kt * BKW) / AQ;
   // packed: the exclusive end of the workgroup's query-tile loop (clamped into the causal walk) and the wave's last tile
-  int qend = nqt, qhiw = nqt;
+  // (bidirectional: the tiles that hold a query < L)
+  int qend = BIDIR ? (L + AQ - 1) / AQ : nqt, qhiw = nqt;
   if constexpr (PACKED) {
     const int* deb = doc_end + (int64_t)b * T;
     const int ew = __builtin_amdgcn_readfirstlane(deb[min(kt * BKW + BKW - 1, T - 1)]);
@@ -883,7 +961,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
     constexpr int cur = decltype(bufc)::value;
     const bool more = qt + 1 < qend;
     if (more) dma_tile(qt + 1, cur ^ 1);  // in flight during this tile's MFMAs (cur ^ 1 last read before the previous barrier)
-    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask
+    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask, 3 (bidirectional only) query < L
     auto compute = [&](const char* base, auto maskc) __attribute__((always_inline)) {
       constexpr int MK = decltype(maskc)::value;
       constexpr bool MASK = MK == 1;
@@ -945,6 +1023,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
               const bool keep = drop_keep(dm[r][mt], e, dr.thr);
               ps[r][mt][e] = keep ? p : 0.f;                                   // P o M (s in the final dV)
               dp[r][mt][e] = p * fmaf(dp[r][mt][e], keep ? dscale : 0.f, ndd[e]);  // dS = P (M s dP - delta)
+            } else if constexpr (MK == 3) {  // a padding query: P and dS are 0 by select, whatever its lse / dO hold
+              const bool vis = qt * AQ + 16 * mt + 4 * g + e < L;
+              ps[r][mt][e] = vis ? p : 0.f;
+              dp[r][mt][e] = vis ? p * dp[r][mt][e] : 0.f;
             } else {
               ps[r][mt][e] = p;                        // P
               dp[r][mt][e] = p * dp[r][mt][e];  // dS (unscaled)
@@ -978,6 +1060,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
         else if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
         else compute(smem + cur * BUF, std::integral_constant<int, 1>{});
       }
+    } else if constexpr (BIDIR) {
+      if (k0w < L) {  // a wave past L only stages its pieces of the tiles
+        // the query tiles below qfull are full; kept in a VGPR for a per-wave branch, as kd in attn_fwd_dma_kernel
+        // (306 -> 234 VGPRs: two waves per SIMD)
+        int qfull = L / AQ;
+        asm volatile("" : "+v"(qfull));
+        if (qt < qfull) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
+        else compute(smem + cur * BUF, std::integral_constant<int, 3>{});
+      }
     } else if (live && qt >= qtw) {
       if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
       else compute(smem + cur * BUF, std::integral_constant<int, 1>{});
@@ -1006,6 +1097,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
       if constexpr (DROP) dv[r][d] *= dscale;
       c[0] = pack_bf2(dv[r][d][0], dv[r][d][1]);
       c[1] = pack_bf2(dv[r][d][2], dv[r][d][3]);
+      if constexpr (BIDIR) {
+        const bool vis = k0w + 16 * r + li < L;
+        a = vis ? a : u32x2{0u, 0u};
+        c = vis ? c : u32x2{0u, 0u};
+      }
       *(u32x2*)(dkb + 16 * d + 4 * g) = a;
       *(u32x2*)(dvb + 16 * d + 4 * g) = c;
     }
@@ -1164,12 +1260,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const uint16_t* __rest
 // wave skips the tiles before its own, and a tile that crosses a document start of the wave masks on both bounds;
 // P of a masked key is 0 by select after the exp2, as for the causal mask.
 // DROP: dS = P (M s dP - delta) with the forward's mask words; the dP chain starts from 0.
-template <bool PACKED, bool DROP>
+// BIDIR: the forward's walk (attn_fwd_dma_kernel) -- key tiles 0 .. ceil(L / 64) - 1, the last one with P and dS of the
+// keys >= L selected to 0 after the exp2.  dQ rows >= L are exact zeros and delta rows >= L are 0.0f.
+template <bool PACKED, bool DROP, bool BIDIR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAVES))) void attn_bwd_dq_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o,
                                                           const uint16_t* __restrict__ dout,
                                                           const float* __restrict__ lse2, float* __restrict__ delta,
                                                           uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
-                                                          float scale, const int* __restrict__ doc_start, AttnDrop dr) {
+                                                          float scale, const int* __restrict__ doc_start, AttnDrop dr,
+                                                          int L) {
+  static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
   // per buffer: K (two d-halves, K-contig) 8K | V (same) 8K | K permuted-row image 8K
   constexpr int KI = 0, VI = 2 * AKV * 64, KP = 4 * AKV * 64, STG = KP + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
@@ -1185,8 +1285,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
   const int q0w = qt * FQ + 32 * w;
   const bool live = q0w < T;
   const int ktw = live ? (q0w + 31) / AKV : -1;
-  const int kd = (q0w + 1) / AKV;  // key tiles below kd need no causal mask
-  const int nkt = min((qt * FQ + FQ - 1) / AKV, T / AKV - 1) + 1;
+  int kd = BIDIR ? L / AKV : (q0w + 1) / AKV;  // key tiles below kd need no mask (bidirectional: are full)
+  if constexpr (BIDIR) asm volatile("" : "+v"(kd));  // a per-wave branch, as in attn_fwd_dma_kernel (222 -> 195 VGPRs)
+  const int nkt = BIDIR ? (L + AKV - 1) / AKV : min((qt * FQ + FQ - 1) / AKV, T / AKV - 1) + 1;
+  if constexpr (BIDIR) {
+    if (qt * FQ >= L) {  // every query of the workgroup is padding (workgroup-uniform: no barrier is left behind)
+      if (live) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int myq = q0w + 16 * r + li;
+          uint16_t* dq = dqkv + ((int64_t)b * T + myq) * RS + (int64_t)h * AD;
+#pragma unroll
+          for (int d = 0; d < 4; ++d) *(u32x2*)(dq + 16 * d + 4 * g) = u32x2{0u, 0u};
+          if (g == 0) delta[(int64_t)bh * T + myq] = 0.f;
+        }
+      }
+      return;
+    }
+  }
 
   // the wave's Q / dO rows as B operands; delta = rowsum(dO * O) from the same lanes (the
   // lane's 16 d-values, then the 4-group permlane reduce), published for the dK/dV kernel
@@ -1209,6 +1325,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
       for (int e = 0; e < 8; ++e) dot = fmaf(fa[e], fb[e], dot);
     }
     dot = rowsum4(dot);
+    if constexpr (BIDIR) dot = myq < L ? dot : 0.f;
     if (live && g == 0) delta[(int64_t)bh * T + myq] = dot;
     lq[r] = lse2[(int64_t)bh * T + myq];
     ndl[r] = -dot;
@@ -1277,7 +1394,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
     constexpr int cur = decltype(bufc)::value;
     const bool more = kt + 1 < nkt;
     if (more) dma_tile(kt + 1, cur ^ 1);  // cur ^ 1 last read before the previous barrier
-    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask
+    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask, 3 (bidirectional only) key < L
     auto compute = [&](const char* s, auto maskc) __attribute__((always_inline)) {
       constexpr int MK = decltype(maskc)::value;
       constexpr bool MASK = MK == 1;
@@ -1312,6 +1429,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
             }
             if constexpr (DROP)  // dS^T = P (M s dP^T - delta); dP^T started from 0
               dp[r][nt][e] = p * fmaf(dp[r][nt][e], drop_keep(dw[nt], e, dr.thr) ? dscale : 0.f, ndl[r]);
+            else if constexpr (MK == 3)  // a padding key: dS is 0 by select, whatever its K / V rows hold
+              dp[r][nt][e] = (kt * AKV + 16 * nt + 4 * g + e < L) ? p * dp[r][nt][e] : 0.f;
             else
               dp[r][nt][e] = p * dp[r][nt][e];  // dS^T (unscaled); dP^T started from -delta
           }
@@ -1330,6 +1449,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
         if (kt * AKV < dshi) compute(smem + cur * STG, std::integral_constant<int, 2>{});
         else if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
         else compute(smem + cur * STG, std::integral_constant<int, 1>{});
+      }
+    } else if constexpr (BIDIR) {
+      if (q0w < L) {  // a wave past L only stages its pieces of the tiles
+        if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
+        else compute(smem + cur * STG, std::integral_constant<int, 3>{});
       }
     } else {
       if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
@@ -1351,6 +1475,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
       u32x2 pk;
       pk[0] = pack_bf2(acc[r][d][0] * scale, acc[r][d][1] * scale);
       pk[1] = pack_bf2(acc[r][d][2] * scale, acc[r][d][3] * scale);
+      if constexpr (BIDIR) pk = q0w + 16 * r + li < L ? pk : u32x2{0u, 0u};
       *(u32x2*)(o + 16 * d + 4 * g) = pk;
     }
   }
@@ -1379,7 +1504,7 @@ extern "C" int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int 
   const dim3 grid(B * H * ((T + FQ - 1) / FQ));
   if (doc_start) {
     if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
-    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, false>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, AttnDrop{});
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, false>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, AttnDrop{}, 0);
     return 0;
   }
 #ifdef DPE_ATTN_FWD_STAGED
@@ -1387,7 +1512,7 @@ extern "C" int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int 
 #else
   if (dma)
     hipLaunchKernelGGL((attn_fwd_dma_kernel<false, false>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, (const int*)nullptr,
-                       AttnDrop{});
+                       AttnDrop{}, 0);
   else
     hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
 #endif
@@ -1407,9 +1532,9 @@ extern "C" int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint
   if (doc_start) {
     if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
     hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<true, false>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, doc_start, AttnDrop{});
+                       sl2, scale, doc_start, AttnDrop{}, 0);
     hipLaunchKernelGGL((attn_bwd_dma_kernel<true, false>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       doc_start, doc_end, AttnDrop{});
+                       doc_start, doc_end, AttnDrop{}, 0);
     return 0;
   }
 #ifdef DPE_ATTN_BWD_STAGED
@@ -1419,9 +1544,9 @@ extern "C" int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint
 #else
   if (dma) {
     hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, false>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, (const int*)nullptr, AttnDrop{});
+                       sl2, scale, (const int*)nullptr, AttnDrop{}, 0);
     hipLaunchKernelGGL((attn_bwd_dma_kernel<false, false>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       (const int*)nullptr, (const int*)nullptr, AttnDrop{});
+                       (const int*)nullptr, (const int*)nullptr, AttnDrop{}, 0);
   } else {
     hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2, scale);
     hipLaunchKernelGGL(attn_bwd_kernel, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale);
@@ -1443,10 +1568,10 @@ extern "C" int dpe_attn_fwd_drop(const uint16_t* qkv, uint16_t* out, float* lse,
   const dim3 grid(B * H * ((T + FQ - 1) / FQ));
   const AttnDrop dr{rng, stream, thr};
   if (doc_start)
-    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, true>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, dr);
+    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, true>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, dr, 0);
   else
     hipLaunchKernelGGL((attn_fwd_dma_kernel<false, true>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2,
-                       (const int*)nullptr, dr);
+                       (const int*)nullptr, dr, 0);
   return 0;
 }
 
@@ -1463,14 +1588,42 @@ extern "C" int dpe_attn_bwd_drop(const uint16_t* qkv, const uint16_t* out, const
   // dQ first: it also writes delta = rowsum(dO * O) (O is the dropped output), which the dK/dV kernel reads
   if (doc_start) {
     hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<true, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, doc_start, dr);
+                       sl2, scale, doc_start, dr, 0);
     hipLaunchKernelGGL((attn_bwd_dma_kernel<true, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       doc_start, doc_end, dr);
+                       doc_start, doc_end, dr, 0);
   } else {
     hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, (const int*)nullptr, dr);
+                       sl2, scale, (const int*)nullptr, dr, 0);
     hipLaunchKernelGGL((attn_bwd_dma_kernel<false, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       (const int*)nullptr, (const int*)nullptr, dr);
+                       (const int*)nullptr, (const int*)nullptr, dr, 0);
   }
+  return 0;
+}
+
+// Bidirectional attention over the first seq_len rows (1 <= seq_len <= T; the rows from seq_len on are padding: out and
+// dqkv get exact zeros there).  LDS-DMA kernels only, no doc_start, no dropout: a shape or switch that would take the
+// register-staged kernels is an error, as for packed documents.
+extern "C" int dpe_attn_fwd_bidir(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale,
+                                  int seq_len, hipStream_t st) {
+  if (D != AD || T % AKV != 0 || seq_len < 1 || seq_len > T) return -1;
+  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  hipLaunchKernelGGL((attn_fwd_dma_kernel<false, false, true>), dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out,
+                     lse, B, T, H, sl2, (const int*)nullptr, AttnDrop{}, seq_len);
+  return 0;
+}
+
+extern "C" int dpe_attn_bwd_bidir(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
+                                  float* delta, uint16_t* dqkv, int B, int T, int H, int D, float scale, int seq_len,
+                                  hipStream_t st) {
+  if (D != AD || T % AKV != 0 || seq_len < 1 || seq_len > T) return -1;
+  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 gq(B * H * ((T + FQ - 1) / FQ)), gk(B * H * ((T + BKW - 1) / BKW));
+  // dQ first: it also writes delta = rowsum(dO * O), which the dK/dV kernel reads
+  hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, false, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T,
+                     H, sl2, scale, (const int*)nullptr, AttnDrop{}, seq_len);
+  hipLaunchKernelGGL((attn_bwd_dma_kernel<false, false, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2,
+                     scale, (const int*)nullptr, (const int*)nullptr, AttnDrop{}, seq_len);
   return 0;
 }

@@ -259,6 +259,30 @@ __global__ __launch_bounds__(ET) void nchw_to_nhwc_kernel(const float* __restric
   }
 }
 
+// x NCHW f32 [N,C,H,W] -> patch rows bf16 [N, (H/p)(W/p), C p p], a row ordered (c, py, px): the flattened patch-embedding
+// filter [D, C, p, p] is then the GEMM weight.  p % 8 == 0: a thread owns 8 consecutive px of one (c, py) line, two 16-B
+// loads (32-B aligned: W % p == 0), one RNE rounding, one 16-B store.
+__global__ __launch_bounds__(ET) void patchify_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int N, int C, int H,
+                                                      int W, int p) {
+  const int p8 = p / 8, gw = W / p, gh = H / p;
+  const int64_t total = (int64_t)N * gh * gw * C * p * p8;
+  GRID_STRIDE(i, total) {  // i = ((((n gh + ty) gw + tx) C + c) p + py) p8 + x8: 8 * i is the output element
+    int64_t t = i;
+    const int x8 = (int)(t % p8); t /= p8;
+    const int py = (int)(t % p); t /= p;
+    const int c = (int)(t % C); t /= C;
+    const int tx = (int)(t % gw); t /= gw;
+    const int ty = (int)(t % gh);
+    const int64_t n = t / gh;
+    const float* src = x + ((n * C + c) * H + (int64_t)ty * p + py) * W + tx * p + 8 * x8;
+    const f32x4 a = *(const f32x4*)src, b = *(const f32x4*)(src + 4);
+    u32x4 r;
+    r[0] = pack_bf2(a[0], a[1]); r[1] = pack_bf2(a[2], a[3]);
+    r[2] = pack_bf2(b[0], b[1]); r[3] = pack_bf2(b[2], b[3]);
+    *(u32x4*)(y + i * 8) = r;
+  }
+}
+
 // x NCHW f32 [N,C<=4,H,W] -> space-to-depth NHWC bf16 [N,H/2,W/2,16],
 // channel (ay*2+ax)*4+c = x[n][c][2q+ay][2p+ax] (zeros for c >= C).  The 7x7/s2
 // stem then runs as a 4x4/s1 conv over 16 channels (K 256 instead of 392, two
@@ -496,6 +520,12 @@ extern "C" int dpe_conv_w_flipT_multi(const void* desc, const int* start, int n,
   if (n <= 0 || total_blocks <= 0) return 0;
   hipLaunchKernelGGL(conv_w_flipT_multi_kernel, dim3(total_blocks), dim3(256), 0, st, (const FlipDesc*)desc, start, n);
   return (int)hipGetLastError();
+}
+
+extern "C" int dpe_patchify(const float* x, uint16_t* y, int N, int C, int H, int W, int p, hipStream_t st) {
+  if (p < 8 || p % 8 != 0 || H % p != 0 || W % p != 0 || N < 1 || C < 1) return -1;
+  hipLaunchKernelGGL(patchify_kernel, dim3(egrid((int64_t)N * C * H * W / 8)), dim3(ET), 0, st, x, y, N, C, H, W, p);
+  return 0;
 }
 
 extern "C" int dpe_nchw_to_nhwc(const float* x, uint16_t* y, int N, int C, int HW, int Cp, hipStream_t st) {

@@ -110,6 +110,8 @@ int dpe_add(const void* a, const void* b, void* out, int64_t n, float alpha, int
 int dpe_colsum(const void* dy, int64_t M, int N, int64_t ld, float* db, int accumulate, int bf16, hipStream_t st);
 int dpe_nchw_to_s2d(const float* x, uint16_t* y, int N, int C, int H, int W, hipStream_t st);
 int dpe_nchw_to_nhwc(const float* x, uint16_t* y, int N, int C, int HW, int Cp, hipStream_t st);
+// x NCHW f32 -> y bf16 [N, (H/p)(W/p), C p p], rows ordered (c, py, px); p % 8 == 0, H % p == W % p == 0
+int dpe_patchify(const float* x, uint16_t* y, int N, int C, int H, int W, int p, hipStream_t st);
 int dpe_conv_w_flipT(const uint16_t* w, uint16_t* wt, int K, int R, int S, int C, int r0, int rs, int Rp, int s0, int ss,
                      int Sp, hipStream_t st);
 int dpe_flip_desc_bytes();
@@ -174,6 +176,12 @@ int dpe_attn_fwd_drop(const uint16_t* qkv, uint16_t* out, float* lse, int B, int
 int dpe_attn_bwd_drop(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                       uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, const int32_t* doc_start,
                       const int32_t* doc_end, const int64_t* rng, uint32_t stream, uint32_t thr, hipStream_t st);
+// bidirectional attention over the first seq_len rows (1 <= seq_len <= T; out / dqkv rows from seq_len on are zeros);
+// LDS-DMA kernels only, no doc_start, no dropout
+int dpe_attn_fwd_bidir(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int seq_len,
+                       hipStream_t st);
+int dpe_attn_bwd_bidir(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
+                       uint16_t* dqkv, int B, int T, int H, int D, float scale, int seq_len, hipStream_t st);
 // ---- decode.hip
 // one query per (b, h) against the head-major cache kc / vc [B, H, Tmax, 64]; qkv_step [B, 3, H, 64]; len int32 [B]
 // (clamped into [0, Tmax - 1]); S key splits (ws: dpe_attn_decode_ws_floats fp32, unused for S = 1); out [B, H * 64]

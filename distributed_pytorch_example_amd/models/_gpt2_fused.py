@@ -205,7 +205,12 @@ class BlockFn(Function):
         h1, m1, r1 = C.layernorm_fwd(x, blk.ln_1.weight.detach(), opt(blk.ln_1.bias), blk.ln_1.eps)
         qkv = C.linear_fwd(h1, shadow(blk.c_attn.weight), opt(blk.c_attn.bias), 0, False, None, None)
         qkv5 = qkv.view(B, T, 3, H, hd)
-        if drop is not None:
+        bidir = getattr(blk, "seq_len", None)  # Block's attention mode: None causal, else the bidirectional key bound
+        if bidir is not None:
+            if drop is not None or doc is not None:
+                raise ValueError("the bidirectional block takes neither dropout nor packed documents")
+            a, lse = C.attn_fwd(qkv5, H, scale, False, seq_len=bidir)
+        elif drop is not None:
             # dropout (p, rng snapshot, first stream): on P inside the attention kernels; the projections write
             # bf16 and dropout_add forms the fp32 x + dropout(proj) (no fp32-residual GEMM epilogue here)
             dp, rng, ds0 = drop
@@ -231,7 +236,7 @@ class BlockFn(Function):
         else:
             y = C.linear_fwd(u, shadow(blk.mlp_proj.weight), opt(blk.mlp_proj.bias), 0, True, x2, None)
         ctx.save_for_backward(x, h1, m1, r1, qkv5, a, lse, x2, h2, m2, r2, v, u)
-        ctx.blk, ctx.scale, ctx.doc, ctx.drop = blk, scale, doc, drop
+        ctx.blk, ctx.scale, ctx.doc, ctx.drop, ctx.bidir = blk, scale, doc, drop, bidir
         for p in params:
             note_use(p)
         return y
@@ -314,7 +319,9 @@ class BlockFn(Function):
             g2b = C.dropout_cast(g2, drop[0], drop[1], drop[2] + 1)
         da = linear_bwd(blk.attn_proj, g2b, a)
         a4 = a.view(qkv5.shape[0], qkv5.shape[1], qkv5.shape[3], qkv5.shape[4])
-        if drop is not None:
+        if ctx.bidir is not None:
+            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, False, seq_len=ctx.bidir)
+        elif drop is not None:
             dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True,
                               doc_start=None if ctx.doc is None else ctx.doc[0],
                               doc_end=None if ctx.doc is None else ctx.doc[1], dropout_p=drop[0], rng=drop[1], stream=drop[2])

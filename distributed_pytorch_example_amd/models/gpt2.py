@@ -49,10 +49,15 @@ class GPT2Config:
 
 
 class Block(nn.Module):
-    def __init__(self, cfg: GPT2Config):
+    """``seq_len``: the attention mode.  None (the default) is causal attention; an integer L is bidirectional
+    attention over the first L rows of a sequence padded to whole 64-key tiles (models/vit.py) -- the rows from L on
+    are padding, and no dropout or packed documents go with it."""
+
+    def __init__(self, cfg, seq_len=None):
         super().__init__()
         d = cfg.n_embd
         self.n_head = cfg.n_head
+        self.seq_len = None if seq_len is None else int(seq_len)
         self.ln_1 = LayerNorm(d, bias=cfg.bias)
         self.c_attn = Linear(d, 3 * d, bias=cfg.bias)
         self.attn_proj = Linear(d, d, bias=cfg.bias)
@@ -71,6 +76,8 @@ class Block(nn.Module):
         ``drop``: None, or (p, rng, stream) for a training forward with dropout -- p the rate, rng the forward's
         DropoutState snapshot (None off the GPU), stream the layer's first call-site id (attention; + 1 the
         attention residual, + 2 the MLP residual)."""
+        if self.seq_len is not None and (drop is not None or doc is not None):
+            raise ValueError("the bidirectional block takes neither dropout nor packed documents")
         # (the fused block calls the attention kernels directly: only for the shapes they take)
         if (x.is_cuda and self.fused and torch.is_grad_enabled()
                 and Fx.attn_kernel_ok(x.shape[1], x.shape[2] // self.n_head)):
@@ -89,7 +96,10 @@ class Block(nn.Module):
             return Fx.dropout_add(x, self.mlp_proj(u), p, rng, stream + 2)
         h = self.ln_1(x)
         qkv = self.c_attn(h)
-        a = Fx.causal_attention(qkv, self.n_head) if doc is None else Fx.causal_attention(qkv, self.n_head, doc)
+        if self.seq_len is not None:
+            a = Fx.attention(qkv, self.n_head, self.seq_len)
+        else:
+            a = Fx.causal_attention(qkv, self.n_head) if doc is None else Fx.causal_attention(qkv, self.n_head, doc)
         x = Fx.linear_residual(a, self.attn_proj.weight, self.attn_proj.bias, x)
         h = self.ln_2(x)
         u = Fx.gelu(self.c_fc(h))

@@ -972,6 +972,65 @@ def causal_attention(qkv, n_head: int, doc_bounds=None, dropout_p: float = 0.0, 
     return out.reshape(B, T, n_head * D)
 
 
+class _BidirAttnFn(Function):
+    """Bidirectional attention over the first ``seq_len`` rows on the LDS-DMA kernels (causal=False); the rows from
+    ``seq_len`` on are padding: zeros in the output and in all three parts of the gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, H: int, scale: float, seq_len: int):
+        out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, False, seq_len=seq_len)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.H, ctx.scale, ctx.seq_len = H, scale, seq_len
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, False,
+                              seq_len=ctx.seq_len)
+        return dqkv, None, None, None
+
+
+def _attention_torch(qkv5, scale: float, seq_len: int):
+    """The bidirectional form of _causal_attention_torch: query i < seq_len sees the keys j < seq_len, the rows from
+    seq_len on are zeros (and pass no gradient); fp32 softmax, result in qkv's dtype."""
+    T = qkv5.shape[1]
+    q, k, v = qkv5[:, :seq_len].float().permute(2, 0, 3, 1, 4)  # each [B, H, L, D]: the padding rows never enter
+    o = torch.softmax((q @ k.transpose(-1, -2)) * scale, dim=-1) @ v
+    o = F.pad(o.transpose(1, 2), (0, 0, 0, 0, 0, T - seq_len))  # [B, T, H, D], zeros from seq_len on
+    return o.to(qkv5.dtype)
+
+
+def attention(qkv, n_head: int, seq_len: Optional[int] = None):
+    """qkv: [B, Tp, 3*H*D] -> [B, Tp, H*D] softmax attention without the causal mask over the first ``seq_len`` rows
+    (default Tp): query i < seq_len sees the keys j < seq_len; the rows from seq_len on are padding and come back as
+    zeros, in the output and in the gradient.  On the GPU with attn_kernel_ok(Tp, D) the flash kernels run; elsewhere
+    an explicit fp32 masked softmax in torch ops with the same semantics."""
+    B, T, three_hd = qkv.shape
+    D = three_hd // (3 * n_head)
+    L = T if seq_len is None else int(seq_len)
+    if not 1 <= L <= T:
+        raise ValueError(f"seq_len must be in [1, {T}], got {seq_len}")
+    scale = 1.0 / math.sqrt(D)
+    if not qkv.is_cuda or not attn_kernel_ok(T, D):
+        return _attention_torch(qkv.reshape(B, T, 3, n_head, D), scale, L).reshape(B, T, n_head * D)
+    return _BidirAttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, L).reshape(B, T, n_head * D)
+
+
+def patchify(x: torch.Tensor, patch: int) -> torch.Tensor:
+    """NCHW fp32 image batch [B, C, H, W] -> patch rows [B, (H/p)(W/p), C*p*p], each row ordered (c, py, px), so a
+    patch-embedding filter [D, C, p, p] flattened is the ``linear`` weight.  bf16 from one kernel on the GPU (one RNE
+    rounding); on the CPU unfold / reshape in x's dtype, like to_nhwc_input.  The input has no gradient."""
+    B, C, H, W = x.shape
+    p = int(patch)
+    if H % p or W % p:
+        raise ValueError(f"patch {p} must divide the image size {H} x {W}")
+    if not x.is_cuda:
+        y = x.detach().reshape(B, C, H // p, p, W // p, p).permute(0, 2, 4, 1, 3, 5)
+        return y.reshape(B, (H // p) * (W // p), C * p * p).contiguous()
+    return ext().patchify(x.detach().float().contiguous(), p)
+
+
 def add(a, b):
     if not a.is_cuda:
         return a + b

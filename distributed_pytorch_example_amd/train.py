@@ -45,7 +45,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--checkpoint-dir", type=str, default="./checkpoints")
     p.add_argument("--resume", type=str, default=None)
     # ---- additive
-    p.add_argument("--model", default="simplenet", choices=["simplenet", "resnet50", "resnet_tiny", "gpt2", "gpt2-tiny"])
+    p.add_argument("--model", default="simplenet", choices=["simplenet", "resnet50", "resnet_tiny", "gpt2", "gpt2-tiny",
+                                                                   "vit-tiny", "vit-s16", "vit-b16"])
     p.add_argument("--backend", default="auto", choices=["auto", "rccl", "nccl", "gloo"])
     p.add_argument("--dtype", default=None, choices=[None, "fp32", "bf16"],
                    help="compute dtype on the GPU (default: fp32 for simplenet as the reference, bf16 otherwise; "
@@ -104,7 +105,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--grad-accum", type=int, default=1)
     p.add_argument("--seed", type=int, default=None, help="seed the synthetic data (reference: unseeded)")
     p.add_argument("--loader", default="auto", choices=["auto", "device", "torch"])
-    p.add_argument("--image-size", type=int, default=224)
+    p.add_argument("--image-size", type=int, default=None,
+                   help="resnet and vit models: the square input size (default 224; vit-tiny 32)")
     p.add_argument("--seq-len", type=int, default=1024)
     p.add_argument("--doc-len-mean", type=float, default=None,
                    help="gpt2 models: pack documents of this mean length (geometric) into every row; attention stays "
@@ -131,9 +133,9 @@ def _datasets(args, device):
         tr = SyntheticDataset(args.num_samples, 784, 10, seed=args.seed)
         va = SyntheticDataset(args.num_samples // 10, 784, 10, seed=None if args.seed is None else args.seed + 1)
         return tr, va, 10
-    if args.model.startswith("resnet"):
+    if args.model.startswith(("resnet", "vit")):
         shp = (3, args.image_size, args.image_size)
-        ncls = 1000 if args.model == "resnet50" else 10
+        ncls = 1000 if args.model in ("resnet50", "vit-s16", "vit-b16") else 10
         tr = SyntheticDataset(args.num_samples, shp, ncls, seed=args.seed)
         va = SyntheticDataset(max(1, args.num_samples // 10), shp, ncls, seed=None if args.seed is None else args.seed + 1)
         return tr, va, ncls
@@ -253,6 +255,18 @@ def _dtype_kw(args) -> dict:
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    vit = args.model.startswith("vit")
+    if args.image_size is None:
+        args.image_size = 32 if args.model == "vit-tiny" else 224
+    if vit:
+        # the mixed input pack emits ResNet's layouts, and the bidirectional blocks take no dropout or packed documents
+        for flag, on in (("--mixup-alpha", args.mixup_alpha != 0.0), ("--cutmix-alpha", args.cutmix_alpha != 0.0),
+                         ("--dropout", args.dropout != 0.0), ("--doc-len-mean", args.doc_len_mean is not None)):
+            if on:
+                parser.error(f"{flag} is not available for the vit models")
+        patch = 8 if args.model == "vit-tiny" else 16
+        if args.image_size < patch or args.image_size % patch:
+            parser.error(f"--image-size must be a positive multiple of the patch size {patch} for {args.model}")
     if args.skip_nonfinite_steps and args.clip_grad_norm is None:
         parser.error("--skip-nonfinite-steps needs --clip-grad-norm")
     if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
@@ -316,7 +330,8 @@ def main(argv=None):
     logger.info(f"Configuration: epochs={args.epochs}, batch_size={args.batch_size}, lr={args.lr}")
 
     reg_kw = {"label_smoothing": args.label_smoothing, "z_loss": args.z_loss, "dropout": args.dropout}
-    model = get_model(args.model, **_dtype_kw(args), **(reg_kw if args.model.startswith("gpt2") else {})).to(device)
+    model_kw = reg_kw if args.model.startswith("gpt2") else ({"image_size": args.image_size} if vit else {})
+    model = get_model(args.model, **_dtype_kw(args), **model_kw).to(device)
     model = DDP(model, bucket_cap_mb=args.bucket_mb,
                 last_bucket_mb="auto" if args.last_bucket_mb is None else (args.last_bucket_mb or None),
                 gradient_compression=None if args.gradient_compression == "none" else args.gradient_compression,
