@@ -70,4 +70,5 @@ void register_conv(pybind11::module& m);  // conv.cpp
 void register_bn(pybind11::module& m);    // bn.cpp
 void register_ops(pybind11::module& m);   // ops.cpp
 void register_decode(pybind11::module& m);  // decode.cpp
+void register_dwconv(pybind11::module& m);  // dwconv.cpp
 }  // namespace dpe_ops

@@ -75,6 +75,15 @@ int dpe_wgrad3x3_rows_blocks(int N, int H, int W);
 int64_t dpe_wgrad3x3_rows_scratch(int nb);
 int dpe_wgrad3x3_rows_launch(const uint16_t* x, const uint16_t* dy, float* dw, float* scratch, int N, int H, int W, int nb,
                              float alpha, const float* in_coef, hipStream_t st);
+// ---- dwconv.hip
+// depthwise 7x7 / stride 1 / pad 3 on NHWC, C % 8 == 0; x bf16 or fp32 (rounded to bf16 once), w49 [49][C] bf16 taps
+// (the data gradient: dy as x, the taps reversed, no bias); y bf16
+int dpe_dwconv7_fwd(const void* x, int x_f32, const uint16_t* w49, const float* bias, uint16_t* y, int N, int H, int W, int C,
+                    hipStream_t st);
+int64_t dpe_dwconv7_wgrad_blocks(int N, int H, int W, int C);  // partials: part holds blocks * C * 50 floats
+// dw [C][49] and db [C] (or null), fp32, written or (accumulate) added to
+int dpe_dwconv7_wgrad(const uint16_t* dy, const void* x, int x_f32, float* part, float* dw, float* db, int accumulate, int N,
+                      int H, int W, int C, hipStream_t st);
 // ---- loss.hip
 int dpe_cross_entropy(const void* logits, int in_bf16, const int64_t* labels, int B, int V, int64_t ld, float grad_scale,
                       void* dlogits, int out_bf16, float* loss_rows, float* loss_sum, float* correct, int ignore_index,

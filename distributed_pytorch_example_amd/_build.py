@@ -34,8 +34,13 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # hgemm.hip: the schedule's claim atomics are issued by one lane and consumed phases later; the
 # atomic optimizer rewrites a uniform-address add into a wave-wide add plus a per-lane offset
 # (readfirstlane of the result), which puts a vmcnt(0) wait right behind the atomic.
+# dwconv.hip: packed fp32 ops off.  Left on, the compiler pairs the channel pair's FMA chains into 784 v_pk_fma_f32
+# and dwconv7_rows_kernel goes from 173 / 181 VGPRs and no scratch to 256 VGPRs and 972 / 1000 B of scratch per lane
+# (bf16 / fp32 input); the kernels are specified scratch-free.  -fno-slp-vectorize alone gives the same ISA today; the
+# target feature holds whichever pass would form the packed ops.
 FILE_FLAGS = {"attn.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
-              "hgemm.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+              "hgemm.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+              "dwconv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _torch_dirs():

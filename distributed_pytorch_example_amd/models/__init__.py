@@ -1,4 +1,5 @@
-"""Model zoo: the reference's SimpleNet plus the BASELINE-scope ResNet-50 and GPT-2-small, and ViT (vit.py)."""
+"""Model zoo: the reference's SimpleNet plus the BASELINE-scope ResNet-50 and GPT-2-small, ViT (vit.py) and ConvNeXt
+(convnext.py)."""
 from .simplenet import SimpleNet
 from .resnet import ResNet, resnet50, resnet18_like
 
@@ -30,6 +31,10 @@ def get_model(name: str, **kw):
         if name == "vit-tiny":
             return ViT(ViTConfig.tiny(**kw))
         return ViT(ViTConfig(**{**VIT_MODELS[name], **kw}))
+    if name in ("convnext-tiny", "convnext-test"):
+        from .convnext import ConvNeXt, ConvNeXtConfig
+
+        return ConvNeXt(ConvNeXtConfig.tiny_test(**kw) if name == "convnext-test" else ConvNeXtConfig(**kw))
     raise ValueError(f"unknown model {name!r}")
 
 

@@ -392,6 +392,78 @@ def conv2d_nhwc(x, weight, stride=(1, 1), padding=(0, 0), dilation=(1, 1), want_
     return _ConvFn.apply(x.contiguous(), weight, w16, stride, padding, dilation, want_stats)
 
 
+# ============================================================ depthwise 7x7
+def _dw_taps(w):  # master [C, 1, 7, 7] -> the kernels' tap-major [49, C] bf16 image
+    return w.reshape(w.shape[0], 49).t().contiguous().to(torch.bfloat16)
+
+
+def _dw_taps_flipped(w):  # the filter rotated by 180 degrees: the data gradient's taps
+    return w.reshape(w.shape[0], 49).flip(1).t().contiguous().to(torch.bfloat16)
+
+
+class _DWConvFn(Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from ._state import derived_shadow
+
+        y = ext().dwconv7_fwd(x, derived_shadow(weight, "dw49", _dw_taps), bias.detach() if bias is not None else None)
+        ctx.save_for_backward(x)
+        ctx.weight, ctx.bias = weight, bias
+        note_use(weight)
+        if bias is not None:
+            note_use(bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from ._state import derived_shadow
+
+        C = ext()
+        (x,) = ctx.saved_tensors
+        weight, bias = ctx.weight, ctx.bias
+        dy = (dy if dy.dtype == torch.bfloat16 else dy.to(torch.bfloat16)).contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = C.dwconv7_dgrad(dy, derived_shadow(weight, "dw49f", _dw_taps_flipped))
+            if x.dtype != torch.bfloat16:
+                dx = dx.to(x.dtype)
+        want_b = bias is not None and ctx.needs_input_grad[2]
+        gw = gb = None
+        if ctx.needs_input_grad[1] or want_b:
+            # one launch writes both; a gradient that is not wanted lands in a scratch buffer
+            buf, direct = grad_sink(weight) if ctx.needs_input_grad[1] else (torch.empty_like(weight), False)
+            bbuf, bdirect = grad_sink(bias) if want_b else (None, False)
+            if direct == bdirect or bbuf is None:
+                C.dwconv7_wgrad(dy, x, buf, bbuf, direct)
+            else:  # one sink accumulates, the other is fresh
+                tmp = torch.empty_like(bbuf)
+                C.dwconv7_wgrad(dy, x, buf, tmp, direct)
+                if bdirect:
+                    bbuf.add_(tmp)
+                else:
+                    bbuf.copy_(tmp)
+            if ctx.needs_input_grad[1]:
+                grad_done(weight, direct)
+                gw = None if direct else buf
+            if want_b:
+                grad_done(bias, bdirect)
+                gb = None if bdirect else bbuf
+        return dx, gw, gb
+
+
+def depthwise_conv2d_nhwc(x, weight, bias=None):
+    """Depthwise 7x7 / stride 1 / pad 3 convolution.  x: [N, H, W, C] (GPU: bf16 or fp32, C % 8 == 0, bf16 out),
+    weight: the fp32 master [C, 1, 7, 7] (torch's depthwise layout), bias: [C] fp32 or None."""
+    if tuple(weight.shape[1:]) != (1, 7, 7) or x.dim() != 4 or x.shape[-1] != weight.shape[0]:
+        raise ValueError(f"depthwise_conv2d_nhwc: x [N, H, W, C] and weight [C, 1, 7, 7], got {tuple(x.shape)} and "
+                         f"{tuple(weight.shape)}")
+    if not x.is_cuda:
+        w = weight + (_emu_w(weight) - weight).detach() if EMULATE_BF16 else weight
+        y = F.conv2d(_emu(x.permute(0, 3, 1, 2).float()), w, bias, padding=3, groups=weight.shape[0])
+        return _emu(y.permute(0, 2, 3, 1).contiguous())
+    return _DWConvFn.apply(x.contiguous(), weight, bias)
+
+
 # ================================================ space-to-depth ResNet stem
 # A 7x7/s2/p3 conv over x equals a 4x4/s1 conv over the space-to-depth image
 # x'[q][p][(ay,ax,c)] = x[2q+ay][2p+ax][c], padded 2 (top/left) and 1

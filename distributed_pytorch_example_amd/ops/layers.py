@@ -95,6 +95,23 @@ class Conv2d(nn.Module):
                 f"padding={self.padding}, layout=NHWC/OHWI")
 
 
+class DepthwiseConv2d(nn.Module):
+    """Depthwise 7x7 / stride 1 / pad 3 NHWC convolution, filter in torch's depthwise layout [C, 1, 7, 7]."""
+
+    def __init__(self, channels: int, bias: bool = True, device=None):
+        super().__init__()
+        self.channels = channels
+        self.weight = nn.Parameter(torch.empty(channels, 1, 7, 7, device=device))
+        self.bias = nn.Parameter(torch.zeros(channels, device=device)) if bias else None
+        nn.init.trunc_normal_(self.weight, std=0.02)  # the ConvNeXt initialisation
+
+    def forward(self, x):
+        return Fx.depthwise_conv2d_nhwc(x, self.weight, self.bias)
+
+    def extra_repr(self):
+        return f"{self.channels}, kernel_size=(7, 7), padding=3, groups={self.channels}, bias={self.bias is not None}"
+
+
 class BatchNorm2d(nn.Module):
     """BatchNorm over the channel (last) dim of NHWC activations, optional fused ReLU / residual add."""
 
