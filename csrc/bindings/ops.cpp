@@ -595,19 +595,37 @@ void bidir_args(const c10::optional<Tensor>& doc_start, const c10::optional<Tens
   TORCH_CHECK(seq_len >= 0 && seq_len <= T, "attn: seq_len must be in [1, T] (0 = T), got ", seq_len);
 }
 
+// n_kv_head > 0: grouped-query attention.  qkv is [B, T, H + 2 * n_kv_head, D] (H query heads, then the key heads, then the
+// value heads), H % n_kv_head == 0; causal only, with or without doc_start / doc_end; no dropout, no seq_len, LDS-DMA
+// kernels only.  0 = one K / V head per query head in the [B, T, 3, H, D] layout: the paths above.
+void gqa_args(int64_t H, int64_t n_kv_head, bool causal, double dropout_p, const c10::optional<Tensor>& rng, int64_t seq_len) {
+  TORCH_CHECK(n_kv_head >= 1 && H % n_kv_head == 0, "attn: H (", H, ") must be a multiple of n_kv_head (", n_kv_head, ")");
+  TORCH_CHECK(causal && seq_len == 0, "attn: n_kv_head goes with causal=True and no seq_len");
+  TORCH_CHECK(dropout_p == 0.0 && !has(rng), "attn: n_kv_head takes no dropout arguments");
+}
+
 std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal, const c10::optional<Tensor>& out_,
                              const c10::optional<Tensor>& lse_, const c10::optional<Tensor>& doc_start,
                              const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng,
-                             int64_t stream, int64_t seq_len) {
+                             int64_t stream, int64_t seq_len, int64_t n_kv_head) {
   CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_CONTIG(qkv);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
-  TORCH_CHECK(qkv.numel() == B * T * 3 * H * D, "attn: qkv must be [B,T,3,H,D]");
+  if (n_kv_head != 0) gqa_args(H, n_kv_head, causal, dropout_p, rng, seq_len);
+  TORCH_CHECK(qkv.numel() == B * T * (n_kv_head ? H + 2 * n_kv_head : 3 * H) * D,
+              "attn: qkv must be [B,T,3,H,D] ([B,T,H+2*n_kv_head,D] with n_kv_head)");
   TORCH_CHECK(D == 64, "attn: head dim 64 supported");
   Tensor out = has(out_) ? *out_ : at::empty({B, T, H, D}, qkv.options());
   Tensor lse = has(lse_) ? *lse_ : at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
   CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out); CHECK_GPU(lse); CHECK_F32(lse); CHECK_CONTIG(lse);
   TORCH_CHECK(out.numel() == B * T * H * D && lse.numel() == B * H * T, "attn_fwd: out is [B,T,H,D], lse [B,H,T]");
   TORCH_CHECK(has(doc_start) == has(doc_end), "attn_fwd: doc_start and doc_end go together");
+  if (n_kv_head != 0) {
+    CHECK_RC(dpe_attn_fwd_gqa(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)n_kv_head, (int)D, (float)scale,
+                              i32_opt(doc_start, B * T, qkv, "attn_fwd: doc_start"),
+                              i32_opt(doc_end, B * T, qkv, "attn_fwd: doc_end"), cur_stream()),
+             "attn_fwd (n_kv_head: LDS-DMA kernels only)");
+    return {out, lse};
+  }
   if (!causal) {
     bidir_args(doc_start, doc_end, dropout_p, rng, seq_len, T);
     CHECK_RC(dpe_attn_fwd_bidir(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale,
@@ -634,14 +652,29 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool ca
 Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const Tensor& lse, int64_t H, double scale,
                 bool causal, const c10::optional<Tensor>& dqkv_, const c10::optional<Tensor>& doc_start,
                 const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng, int64_t stream,
-                int64_t seq_len) {
+                int64_t seq_len, int64_t n_kv_head) {
   CHECK_GPU(qkv); CHECK_BF16(dout); CHECK_CONTIG(dout); CHECK_CONTIG(out);
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
+  if (n_kv_head != 0) {
+    gqa_args(H, n_kv_head, causal, dropout_p, rng, seq_len);
+    CHECK_BF16(qkv); CHECK_CONTIG(qkv); CHECK_GPU(out); CHECK_BF16(out); CHECK_GPU(dout); CHECK_GPU(lse); CHECK_F32(lse);
+    CHECK_CONTIG(lse);
+    TORCH_CHECK(D == 64 && qkv.numel() == B * T * (H + 2 * n_kv_head) * D, "attn_bwd: qkv must be [B,T,H+2*n_kv_head,64]");
+    TORCH_CHECK(out.numel() == B * T * H * D && dout.numel() == out.numel() && lse.numel() == B * H * T,
+                "attn_bwd: out and dout are [B,T,H,D], lse [B,H,T]");
+  }
   Tensor dqkv = has(dqkv_) ? *dqkv_ : at::empty_like(qkv);
   CHECK_GPU(dqkv); CHECK_BF16(dqkv); CHECK_CONTIG(dqkv);
   TORCH_CHECK(dqkv.numel() == qkv.numel(), "attn_bwd: dqkv must have qkv's size");
   Tensor delta = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
   TORCH_CHECK(has(doc_start) == has(doc_end), "attn_bwd: doc_start and doc_end go together");
+  if (n_kv_head != 0) {
+    CHECK_RC(dpe_attn_bwd_gqa(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H,
+                              (int)n_kv_head, (int)D, (float)scale, i32_opt(doc_start, B * T, qkv, "attn_bwd: doc_start"),
+                              i32_opt(doc_end, B * T, qkv, "attn_bwd: doc_end"), cur_stream()),
+             "attn_bwd (n_kv_head: LDS-DMA kernels only)");
+    return dqkv;
+  }
   if (!causal) {
     bidir_args(doc_start, doc_end, dropout_p, rng, seq_len, T);
     CHECK_RC(dpe_attn_bwd_bidir(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
@@ -745,11 +778,11 @@ void register_ops(pybind11::module& m) {
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("causal") = true,
         py::arg("out") = py::none(), py::arg("lse") = py::none(), py::arg("doc_start") = py::none(),
         py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0,
-        py::arg("seq_len") = 0);
+        py::arg("seq_len") = 0, py::arg("n_kv_head") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("H"),
         py::arg("scale"), py::arg("causal") = true, py::arg("dqkv") = py::none(), py::arg("doc_start") = py::none(),
         py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0,
-        py::arg("seq_len") = 0);
+        py::arg("seq_len") = 0, py::arg("n_kv_head") = 0);
   m.def("dropout_add", &dropout_add, py::arg("res"), py::arg("y"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,
         py::arg("out") = py::none(), "fp32 res + dropout(y) (y bf16 or fp32); mask from the device rng state int64[2] (seed, offset) and the stream");
   m.def("dropout_cast", &dropout_cast, py::arg("g"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,

@@ -37,6 +37,9 @@
 //   kernels, described at each; the causal instantiations compile to what they were without the template.
 // Bidirectional attention with a key-length bound (ViT: no causal mask, L of the T rows are real): BIDIR instantiations
 //   of the same three kernels, described at each; every other instantiation compiles to what it was.
+// Grouped-query attention (qkv [B, T, Hq + 2 Hkv, 64]: query heads, then key heads, then value heads): GQA entry points
+//   attn_*_gqa_kernel around the bodies of the same three kernels (attn_dma_*_body.h), described at each; every kernel
+//   from before compiles to what it was.
 #include <type_traits>
 
 #include "common.h"
@@ -108,6 +111,10 @@ DPE_DEVICE float rowsum4(float v) {
   auto s = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(s[0]) + __uint_as_float(s[1]);
 }
+
+// __syncthreads() for the body files: force-inlined, so that it also inlines into the kernels of a DPE_NO_PK_F32 region
+// (the header's own is plain inline, and the inliner leaves a callee whose target features differ as a real call)
+DPE_DEVICE void wg_barrier() { __syncthreads(); }
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
@@ -378,281 +385,30 @@ DPE_DEVICE bool drop_keep(uint32_t word, int byte, uint32_t thr) { return ((word
 // needed.  A workgroup past L stores zeros and leaves; a wave past L only stages its DMA pieces and stores zeros; a
 // wave that straddles L computes all 32 rows and selects zeros at the store.  out rows >= L are exact zeros and
 // lse2 rows >= L are 0.0f.  L chooses loop bounds and masks only, never an address.
+// GQA (grouped-query attention; no DROP, no BIDIR): qkv rows are [Hq query | Hkv key | Hkv value] heads of 64, H = Hq and
+// query head h reads K / V of head h / (Hq / Hkv).  Only the row stride and the K / V bases change; the G query heads of
+// a group are neighbouring workgroups (bh order), so they meet their shared K / V tiles in L2.
+// The GQA kernels are entry points of their own (attn_*_gqa_kernel) around the same body text (attn_dma_*_body.h).
 template <bool PACKED, bool DROP, bool BIDIR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_fwd_dma_kernel(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse2, int B, int T, int H,
     float sl2, const int* __restrict__ doc_start, AttnDrop dr, int L) {
-  static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
-  constexpr int KB = 2 * AKV * 64, STG = KB + AKV * 128;
-  __shared__ __attribute__((aligned(16))) char smem[2 * STG];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
-  const int nq = (T + FQ - 1) / FQ, BH = B * H;
-  const int qt = nq - 1 - (int)(blockIdx.x / BH);
-  const int bh = blockIdx.x % BH, b = bh / H, h = bh % H;
-  const int64_t RS = 3LL * H * AD;
-  const uint16_t* qb = qkv + (int64_t)b * T * RS + (int64_t)h * AD;
-  const uint16_t* kb = qb + H * AD;
-  const int q0w = qt * FQ + 32 * w;
-  const bool live = q0w < T;
-  const int ktw = live ? (q0w + 31) / AKV : -1;
-  const int nkt = BIDIR ? (L + AKV - 1) / AKV : min((qt * FQ + FQ - 1) / AKV, T / AKV - 1) + 1;
-  // packed: first key tile of the workgroup / of the wave, first key no lower mask is needed from, the lane's bounds
-  int kt0 = 0, klo = 0, dshi = 0, ds[2] = {0, 0};
-  if constexpr (PACKED) {
-    const int* dsb = doc_start + (int64_t)b * T;
-    kt0 = min(max(__builtin_amdgcn_readfirstlane(dsb[qt * FQ]) / AKV, 0), nkt - 1);
-    if (live) {
-      klo = __builtin_amdgcn_readfirstlane(dsb[q0w]) / AKV;
-      dshi = __builtin_amdgcn_readfirstlane(dsb[q0w + 31]);
-      ds[0] = dsb[q0w + li];
-      ds[1] = dsb[q0w + 16 + li];
-    }
-  }
-  if constexpr (BIDIR) {
-    if (qt * FQ >= L) {  // every query of the workgroup is padding (workgroup-uniform: no barrier is left behind)
-      if (live) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const int myq = q0w + 16 * r + li;
-          uint16_t* o = out + ((int64_t)(b * T + myq) * H + h) * AD;
-#pragma unroll
-          for (int d = 0; d < 4; ++d) *(u32x2*)(o + 16 * d + 4 * g) = u32x2{0u, 0u};
-          if (g == 0) lse2[(int64_t)bh * T + myq] = 0.f;
-        }
-      }
-      return;
-    }
-  }
-
-  bf16x8 qf[2][2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-      qf[r][kk] = live ? __builtin_bit_cast(bf16x8, *(const u32x4*)(qb + (int64_t)(q0w + 16 * r + li) * RS + 32 * kk + 8 * g))
-                       : bf16x8{};
-
-  // the sequence's qkv rows from K of head h on: one buffer resource, tile advance in soffset
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(kb), (short)0, (int)(T * RS * 2), 0x00020000);
-  uint32_t voff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int o = (w + 4 * i) * 1024 + lane * 16;  // this lane's byte slot in the 16 KiB tile image
-    int key, dc, vo;
-    if (i < 2) {  // K halves: kimg(key, c) = key * 64 + ((c ^ sw(key)) << 4), half dc >> 2
-      const int dh = o >> 12, oo = o & 4095;
-      key = oo >> 6;
-      dc = 4 * dh + (((oo >> 4) & 3) ^ ((0x78 >> (((key >> 2) & 3) << 1)) & 3));
-      vo = 0;
-    } else {      // V: pimg(key, c) = key * 128 + ((c ^ h(key)) << 4)
-      const int oo = o - KB;
-      key = oo >> 7;
-      dc = ((oo >> 4) & 7) ^ (((key >> 1) & 3) << 1);
-      vo = H * AD;
-    }
-    voff[i] = (uint32_t)(((int64_t)key * RS + vo + dc * 8) * 2);
-  }
-  auto dma_tile = [&](int kt, char* s) {
-    const uint32_t so = (uint32_t)((int64_t)kt * AKV * RS * 2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) attn_dma16(rs, s + (w + 4 * i) * 1024, voff[i], so);
-  };
-
-  f32x4 acc[2][4], accl[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    accl[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int d = 0; d < 4; ++d) acc[r][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  float m[2] = {-INFINITY, -INFINITY};
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});
-  // bidirectional: the key tiles below kd are full.  kd is then workgroup-uniform; the empty asm keeps it in a VGPR so the
-  // choice between the two compute paths stays a per-wave (exec) branch as in the causal kernel -- as scalar control flow
-  // the compiler hoists across both paths and spills 36 registers under the 168-VGPR cap
-  int kd = BIDIR ? L / AKV : (q0w + 1) / AKV;
-  if constexpr (BIDIR) asm volatile("" : "+v"(kd));
-  // dropout: the counter of the granule this lane draws (key group nt = li & 3) in key tile 0, per row block
-  [[maybe_unused]] uint64_t dseed = 0, dctr[2] = {0, 0};
-  if constexpr (DROP) {
-    const uint64_t n4 = (uint64_t)(T >> 2);
-    dseed = (uint64_t)dr.rng[0];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-      dctr[r] = (uint64_t)dr.rng[1] + ((uint64_t)bh * n4 + (uint64_t)((q0w + 16 * r + li) >> 2)) * n4 + (uint64_t)(4 * (li & 3) + g);
-  }
-
-  // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask, 3 (bidirectional only) key < L
-  auto compute = [&](int kt, const char* s, auto maskc) __attribute__((always_inline)) {
-    constexpr int MK = decltype(maskc)::value;
-    constexpr bool MASK = MK == 1;
-    f32x4 sc[2][4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const bf16x8 k0 = kfrag64(s, 16 * nt), k1 = kfrag64(s + AKV * 64, 16 * nt);
-#pragma unroll
-      for (int r = 0; r < 2; ++r) sc[r][nt] = MFMA(k1, qf[r][1], MFMA(k0, qf[r][0], zero));
-    }
-    float mc[2];
-    bool need[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      if constexpr (MASK) {
-        const int lim = q0w + 16 * r + li - kt * AKV - 4 * g;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (16 * nt + e > lim) sc[r][nt][e] = -INFINITY;
-      }
-      float mx;
-      if constexpr (MK == 2) {  // the row max over the visible keys only; -inf for a row that sees none here
-        const int lim = q0w + 16 * r + li - kt * AKV - 4 * g, lo = ds[r] - kt * AKV - 4 * g;
-        mx = -INFINITY;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) mx = ((16 * nt + e <= lim) & (16 * nt + e >= lo)) ? fmaxf(mx, sc[r][nt][e]) : mx;
-        mx = rowmax4(mx);
-        mc[r] = mx == -INFINITY ? mx : mx * sl2;
-        need[r] = mc[r] > (m[r] == -INFINITY ? m[r] : m[r] + RESCALE_TH);  // false for a row without a visible key
-      } else if constexpr (MK == 3) {  // the row max over the keys < L; the tile's first key is one, so it is finite
-        const int hi = L - kt * AKV - 4 * g;
-        mx = -INFINITY;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) mx = (16 * nt + e < hi) ? fmaxf(mx, sc[r][nt][e]) : mx;
-        mc[r] = rowmax4(mx) * sl2;
-        need[r] = mc[r] > m[r] + RESCALE_TH;
-      } else {
-        mx = sc[r][0][0];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = (nt == 0); e < 4; ++e) mx = fmaxf(mx, sc[r][nt][e]);
-        mc[r] = rowmax4(mx) * sl2;
-        need[r] = mc[r] > m[r] + RESCALE_TH;
-      }
-    }
-    if (__builtin_amdgcn_ballot_w64(need[0] || need[1])) {
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        float alpha;
-        if constexpr (MK == 2)  // a first visible key: the accumulators are still 0, nothing to rescale
-          alpha = (need[r] & (m[r] != -INFINITY)) ? __builtin_amdgcn_exp2f(m[r] - mc[r]) : 1.f;
-        else
-          alpha = need[r] ? __builtin_amdgcn_exp2f(m[r] - mc[r]) : 1.f;
-        m[r] = need[r] ? mc[r] : m[r];
-        accl[r] *= alpha;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) acc[r][d] *= alpha;
-      }
-    }
-    bf16x8 pk[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      if constexpr (MK == 2) {  // a masked P is 0 by select after the exp2 (which may have overflowed), m = -inf or not
-        const float nm = m[r] == -INFINITY ? 0.f : -m[r];
-        const int lim = q0w + 16 * r + li - kt * AKV - 4 * g, lo = ds[r] - kt * AKV - 4 * g;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float pv = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
-            sc[r][nt][e] = ((16 * nt + e <= lim) & (16 * nt + e >= lo)) ? pv : 0.f;
-          }
-      } else if constexpr (MK == 3) {  // a masked P is 0 by select after the exp2 (which may have overflowed)
-        const float nm = -m[r];
-        const int hi = L - kt * AKV - 4 * g;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float pv = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
-            sc[r][nt][e] = (16 * nt + e < hi) ? pv : 0.f;
-          }
-      } else {
-        const float nm = -m[r];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sc[r][nt][e] = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, nm));
-      }
-      pk[r][0] = pack_frag(sc[r][0], sc[r][1]);
-      pk[r][1] = pack_frag(sc[r][2], sc[r][3]);
-      accl[r] = MFMA(ones, pk[r][1], MFMA(ones, pk[r][0], accl[r]));
-      if constexpr (DROP) {  // l summed the undropped P above; O takes the dropped fragments
-        uint32_t dw[4];
-        drop_words_q(dw, dseed, dctr[r], (uint32_t)kt * (AKV / 4), dr.stream, li & 3);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sc[r][nt][e] = drop_keep(dw[nt], e, dr.thr) ? sc[r][nt][e] : 0.f;
-        pk[r][0] = pack_frag(sc[r][0], sc[r][1]);
-        pk[r][1] = pack_frag(sc[r][2], sc[r][3]);
-      }
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const bf16x8 v0 = trfrag(s + KB, 0, 16 * d), v1 = trfrag(s + KB, 32, 16 * d);
-#pragma unroll
-      for (int r = 0; r < 2; ++r) acc[r][d] = MFMA(v1, pk[r][1], MFMA(v0, pk[r][0], acc[r][d]));
-    }
-  };
-
-  dma_tile(kt0, smem);
-  attn_vm_drain();
-  __syncthreads();
-  // the tile loop unrolled by two: each step's LDS buffer is a compile-time constant
-  auto step = [&](int kt, auto bufc) {
-    constexpr int cur = decltype(bufc)::value;
-    const bool more = kt + 1 < nkt;
-    if (more) dma_tile(kt + 1, smem + (cur ^ 1) * STG);  // read last in step kt - 1, before its barrier
-    if constexpr (PACKED) {
-      if (kt >= klo && kt <= ktw) {
-        if (kt * AKV < dshi) compute(kt, smem + cur * STG, std::integral_constant<int, 2>{});
-        else if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
-        else compute(kt, smem + cur * STG, std::integral_constant<int, 1>{});
-      }
-    } else if constexpr (BIDIR) {
-      if (q0w < L) {  // a wave past L only stages its pieces of the tiles
-        if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
-        else compute(kt, smem + cur * STG, std::integral_constant<int, 3>{});
-      }
-    } else {
-      if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});
-      else if (kt <= ktw) compute(kt, smem + cur * STG, std::integral_constant<int, 1>{});
-    }
-    if (more) attn_vm_drain();
-    __syncthreads();
-  };
-  for (int kt = kt0; kt < nkt; kt += 2) {
-    step(kt, std::integral_constant<int, 0>{});
-    if (kt + 1 < nkt) step(kt + 1, std::integral_constant<int, 1>{});
-  }
-  if (!live) return;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int myq = q0w + 16 * r + li;
-    const float l = accl[r][0];  // every row of the all-ones product is the sum over keys for query li
-    const float inv = (DROP ? 256.f / (float)(256u - dr.thr) : 1.f) / l;
-    uint16_t* o = out + ((int64_t)(b * T + myq) * H + h) * AD;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      u32x2 pk2;
-      pk2[0] = pack_bf2(acc[r][d][0] * inv, acc[r][d][1] * inv);
-      pk2[1] = pack_bf2(acc[r][d][2] * inv, acc[r][d][3] * inv);
-      if constexpr (BIDIR) pk2 = myq < L ? pk2 : u32x2{0u, 0u};
-      *(u32x2*)(o + 16 * d + 4 * g) = pk2;
-    }
-    float ls = m[r] + __log2f(l);
-    if constexpr (BIDIR) ls = myq < L ? ls : 0.f;
-    if (g == 0) lse2[(int64_t)bh * T + myq] = ls;
-  }
+  constexpr bool GQA = false;
+  [[maybe_unused]] const int Hkv = H;
+#include "attn_dma_fwd_body.h"
 }
+DPE_NO_PK_F32_BEGIN
+template <bool PACKED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_fwd_gqa_kernel(
+    const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse2, int B, int T, int Hq, int Hkv,
+    float sl2, const int* __restrict__ doc_start) {
+  constexpr bool GQA = true, DROP = false, BIDIR = false;
+  const int H = Hq;
+  [[maybe_unused]] const AttnDrop dr{};
+  [[maybe_unused]] const int L = 0;
+#include "attn_dma_fwd_body.h"
+}
+DPE_NO_PK_F32_END
 
 // ======================================================================= bwd
 // dK / dV: one workgroup = 128 keys of one (b, h), 4 waves x 32 keys, looping over the
@@ -837,276 +593,37 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
 // BIDIR: the query-tile loop runs over the tiles 0 .. ceil(L / 64) - 1 for every key; the last one (L % 64 != 0) selects
 // P and dS of the queries >= L to 0 after the exp2.  A workgroup past L stores zeros and leaves, a wave past L only
 // stages, a wave that straddles L selects zeros at the store: dK / dV rows >= L are exact zeros.
+// GQA: one workgroup = 128 keys of one KV head (grid B * Hkv * key tiles) and its G = Hq / Hkv query heads.  The
+// query-tile loop becomes one flattened walk over (j, qt), j = 0 .. G - 1 the query head Hkv_index * G + j and qt the
+// causal (or packed) tile range, which is the same for every head: a head change only moves the Q / dO DMA offsets by
+// 64 elements and the lse / delta pointer by one [T] row, so head j + 1's first tile is in flight while head j's last
+// tile computes -- the two-buffer ring is never drained, and its parity runs on across the change (an odd tile count
+// puts head j + 1's first tile in the other buffer).  kf / vf are loaded once and dk / dv stay in the same registers
+// over all G heads: the group sum is the fp32 accumulation itself, rounded to bf16 once at the store -- no atomics, no
+// per-query-head dK / dV and no reduction pass.
 template <bool PACKED, bool DROP, bool BIDIR = false>
 __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
                                                        const float* __restrict__ lse2, const float* __restrict__ delta,
                                                        uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
                                                        float scale, const int* __restrict__ doc_start,
                                                        const int* __restrict__ doc_end, AttnDrop dr, int L) {
-  static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
-  // per buffer: Qk Qm dOk dOm (8 KB each) + lse, delta (512 B) (+ packed: doc_start, 256 B)
-  constexpr int BUF = 4 * 8192 + 512 + (PACKED ? 256 : 0);
-  __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
-  const int nqt = T / AQ, BH = B * H;
-  const int kt = (int)(blockIdx.x / BH);  // heaviest key tiles (most query tiles) first
-  const int bh = blockIdx.x % BH, b = bh / H, h = bh % H;
-  const int64_t RS = 3LL * H * AD;
-  const uint16_t* qb = qkv + (int64_t)b * T * RS + (int64_t)h * AD;
-  const uint16_t* kb = qb + H * AD;
-  const uint16_t* vb = qb + 2 * H * AD;
-  const int64_t ORS = (int64_t)H * AD;  // dO / O row stride
-  const uint16_t* ob = dout + (int64_t)b * T * ORS + (int64_t)h * AD;
-  const int k0w = kt * BKW + 32 * w;  // the wave's first key
-  const bool live = k0w < T;
-  const int qtw = k0w / AQ;           // first query tile that reaches the wave's keys
-  if constexpr (BIDIR) {
-    if (kt * BKW >= L) {  // every key of the workgroup is padding (workgroup-uniform: no barrier is left behind)
-      if (live) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          uint16_t* dkb = dqkv + (int64_t)b * T * RS + (int64_t)(k0w + 16 * r + li) * RS + H * AD + (int64_t)h * AD;
-#pragma unroll
-          for (int d = 0; d < 4; ++d) {
-            *(u32x2*)(dkb + 16 * d + 4 * g) = u32x2{0u, 0u};
-            *(u32x2*)(dkb + H * AD + 16 * d + 4 * g) = u32x2{0u, 0u};
-          }
-        }
-      }
-      return;
-    }
-  }
-
-  // wave's own 32 keys as B operands (key on lane)
-  bf16x8 kf[2][2], vf[2][2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int64_t off = (int64_t)(k0w + 16 * r + li) * RS + 32 * kk + 8 * g;
-      kf[r][kk] = live ? __builtin_bit_cast(bf16x8, *(const u32x4*)(kb + off)) : bf16x8{};
-      vf[r][kk] = live ? __builtin_bit_cast(bf16x8, *(const u32x4*)(vb + off)) : bf16x8{};
-    }
-  // dropout: the counter of the granule this lane draws (query group mt = li & 3) in query tile 0, per row block
-  [[maybe_unused]] uint64_t dseed = 0, dn4 = 0, dctr[2] = {0, 0};
-  [[maybe_unused]] float dscale = 1.f;
-  if constexpr (DROP) {
-    dn4 = (uint64_t)(T >> 2);
-    dseed = (uint64_t)dr.rng[0];
-    dscale = 256.f / (float)(256u - dr.thr);
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-      dctr[r] = (uint64_t)dr.rng[1] + ((uint64_t)bh * dn4 + (uint64_t)(4 * (li & 3) + g)) * dn4 + (uint64_t)((k0w + 16 * r + li) >> 2);
-  }
-  // Q / dO of a query tile: LDS-DMA into [Qk | Qm | Ok | Om] (8 KiB each); lse / -delta via registers
-  float lv = 0.f;
-  [[maybe_unused]] int dsv = 0;
-  const float* pl = (tid < 64 ? lse2 + tid : delta + (tid - 64)) + (int64_t)bh * T;
-  const __amdgpu_buffer_rsrc_t rq =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(qb), (short)0, (int)(T * RS * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdo =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ob), (short)0, (int)(T * ORS * 2), 0x00020000);
-  uint32_t voff[8];  // piece w + 4 i of the 32 KiB image set: i < 4 Q, else dO; (i & 2) permuted-row image
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int oo = ((w + 4 * i) * 1024 + lane * 16) & 8191;  // byte slot inside its 8 KiB image
-    int row, dc;
-    if ((i & 2) == 0) {  // K-contiguous halves: (dc >> 2) * 4096 + kimg(row, dc & 3)
-      const int o2 = oo & 4095;
-      row = o2 >> 6;
-      dc = 4 * (oo >> 12) + (((o2 >> 4) & 3) ^ ((0x78 >> (((row >> 2) & 3) << 1)) & 3));
-    } else {             // permuted-row image: pimg(row, dc)
-      row = oo >> 7;
-      dc = ((oo >> 4) & 7) ^ (((row >> 1) & 3) << 1);
-    }
-    voff[i] = (uint32_t)(((int64_t)row * (i < 4 ? RS : ORS) + dc * 8) * 2);
-  }
-  auto dma_tile = [&](int qt, int buf) {
-    char* base = smem + buf * BUF;
-    const uint32_t sq = (uint32_t)((int64_t)qt * AQ * RS * 2), so = (uint32_t)((int64_t)qt * AQ * ORS * 2);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) attn_dma16(i < 4 ? rq : rdo, base + (w + 4 * i) * 1024, voff[i], i < 4 ? sq : so);
-    if (tid < 128) lv = pl[qt * AQ];
-    if constexpr (PACKED)
-      if (tid >= 128 && tid < 192) dsv = doc_start[(int64_t)b * T + qt * AQ + (tid - 128)];
-  };
-  auto stash = [&](int buf) {  // after the tile's DMA has landed (attn_vm_drain)
-    if (tid < 128) ((float*)(smem + buf * BUF + 4 * 8192))[tid] = tid < 64 ? lv : -lv;  // [0,64) lse, [64,128) -delta
-    if constexpr (PACKED)
-      if (tid >= 128 && tid < 192) ((int*)(smem + buf * BUF + 4 * 8192 + 512))[tid - 128] = dsv;
-  };
-  const int qs = BIDIR ? 0 : (kt * BKW) / AQ;
-  // packed: the exclusive end of the workgroup's query-tile loop (clamped into the causal walk) and the wave's last tile
-  // (bidirectional: the tiles that hold a query < L)
-  int qend = BIDIR ? (L + AQ - 1) / AQ : nqt, qhiw = nqt;
-  if constexpr (PACKED) {
-    const int* deb = doc_end + (int64_t)b * T;
-    const int ew = __builtin_amdgcn_readfirstlane(deb[min(kt * BKW + BKW - 1, T - 1)]);
-    qend = min(max((max(ew, 1) - 1) / AQ + 1, qs + 1), nqt);
-    if (live) qhiw = (max(__builtin_amdgcn_readfirstlane(deb[k0w + 31]), 1) - 1) / AQ;
-  }
-  dma_tile(qs, 0);
-  attn_vm_drain();
-  stash(0);
-  f32x4 dk[2][4], dv[2][4];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int d = 0; d < 4; ++d) { dk[r][d] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[r][d] = dk[r][d]; }
-  __syncthreads();
-
-  // the tile loop unrolled by two: the LDS buffer of each step is a compile-time constant, so every
-  // fragment address is a hoisted per-lane offset plus an immediate
-  auto step = [&](int qt, auto bufc) {
-    constexpr int cur = decltype(bufc)::value;
-    const bool more = qt + 1 < qend;
-    if (more) dma_tile(qt + 1, cur ^ 1);  // in flight during this tile's MFMAs (cur ^ 1 last read before the previous barrier)
-    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask, 3 (bidirectional only) query < L
-    auto compute = [&](const char* base, auto maskc) __attribute__((always_inline)) {
-      constexpr int MK = decltype(maskc)::value;
-      constexpr bool MASK = MK == 1;
-      const char* Qk = base;
-      const char* Qm = base + 8192;
-      const char* Ok = base + 2 * 8192;
-      const char* Om = base + 3 * 8192;
-      const float* sl = (const float*)(base + 4 * 8192);
-      const float* snd = sl + 64;
-      // S[q][key], dP[q][key] - delta[q]: lane = key, rows q = 16mt + 4g + e (the dP chain starts
-      // from -delta, so dS = P * dP' needs no subtraction)
-      // dropout: key on the lane, so of each of its 8 granules the lane needs byte (key % 4) of all four words.
-      // Lane c of the quad draws the granule of query group mt = c (per row block) and turns its bytes (word c' :=
-      // byte c' of words 0..3); the quad transpose then leaves dm[r][mt] = the lane's four bytes of granule mt.
-      [[maybe_unused]] uint32_t dm[2][4];
-      if constexpr (DROP) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const u32x4 a = philox4x32(dseed, dctr[r] + (uint64_t)(uint32_t)(qt * (AQ / 4)) * dn4, dr.stream);
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            dm[r][c] = ((a[0] >> (8 * c)) & 0xffu) | (((a[1] >> (8 * c)) & 0xffu) << 8) | (((a[2] >> (8 * c)) & 0xffu) << 16) |
-                       (((a[3] >> (8 * c)) & 0xffu) << 24);
-          quad_transpose(dm[r], li & 3);
-        }
-      }
-      f32x4 ps[2][4], dp[2][4];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const bf16x8 q0 = kfrag64(Qk, 16 * mt), q1 = kfrag64(Qk + 4096, 16 * mt);
-        const bf16x8 o0 = kfrag64(Ok, 16 * mt), o1 = kfrag64(Ok + 4096, 16 * mt);
-        f32x4 nd4 = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (!DROP) nd4 = *(const f32x4*)(snd + 16 * mt + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          ps[r][mt] = MFMA(q1, kf[r][1], MFMA(q0, kf[r][0], (f32x4{0.f, 0.f, 0.f, 0.f})));
-          dp[r][mt] = MFMA(o1, vf[r][1], MFMA(o0, vf[r][0], nd4));
-        }
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const f32x4 l4 = *(const f32x4*)(sl + 16 * mt + 4 * g);
-        [[maybe_unused]] u32x4 d4;
-        if constexpr (MK == 2) d4 = *(const u32x4*)(base + 4 * 8192 + 512 + 4 * (16 * mt + 4 * g));
-        [[maybe_unused]] f32x4 ndd;
-        if constexpr (DROP) ndd = *(const f32x4*)(snd + 16 * mt + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float p = __builtin_amdgcn_exp2f(fmaf(ps[r][mt][e], sl2, -l4[e]));
-            if constexpr (MASK)
-              if (k0w + 16 * r + li > qt * AQ + 16 * mt + 4 * g + e) p = 0.f;
-            if constexpr (MK == 2) {  // the key is behind the query, or the query's document starts behind the key
-              const int key = k0w + 16 * r + li;
-              p = ((key > qt * AQ + 16 * mt + 4 * g + e) | ((int)d4[e] > key)) ? 0.f : p;
-            }
-            if constexpr (DROP) {
-              const bool keep = drop_keep(dm[r][mt], e, dr.thr);
-              ps[r][mt][e] = keep ? p : 0.f;                                   // P o M (s in the final dV)
-              dp[r][mt][e] = p * fmaf(dp[r][mt][e], keep ? dscale : 0.f, ndd[e]);  // dS = P (M s dP - delta)
-            } else if constexpr (MK == 3) {  // a padding query: P and dS are 0 by select, whatever its lse / dO hold
-              const bool vis = qt * AQ + 16 * mt + 4 * g + e < L;
-              ps[r][mt][e] = vis ? p : 0.f;
-              dp[r][mt][e] = vis ? p * dp[r][mt][e] : 0.f;
-            } else {
-              ps[r][mt][e] = p;                        // P
-              dp[r][mt][e] = p * dp[r][mt][e];  // dS (unscaled)
-            }
-          }
-      }
-      // dV^T += dO^T . P ; dK^T += Q^T . dS   (k = q, permuted order matches the accumulators)
-      bf16x8 pp[2][2], ss[2][2];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        pp[r][0] = pack_frag(ps[r][0], ps[r][1]); pp[r][1] = pack_frag(ps[r][2], ps[r][3]);
-        ss[r][0] = pack_frag(dp[r][0], dp[r][1]); ss[r][1] = pack_frag(dp[r][2], dp[r][3]);
-      }
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const bf16x8 a0 = trfrag(Om, 0, 16 * d), a1 = trfrag(Om, 32, 16 * d);
-        const bf16x8 c0 = trfrag(Qm, 0, 16 * d), c1 = trfrag(Qm, 32, 16 * d);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          dv[r][d] = MFMA(a1, pp[r][1], MFMA(a0, pp[r][0], dv[r][d]));
-          dk[r][d] = MFMA(c1, ss[r][1], MFMA(c0, ss[r][0], dk[r][d]));
-        }
-      }
-    };
-    // query tiles whose first query is past the wave's last key need no causal mask
-    if constexpr (PACKED) {
-      if (live && qt >= qtw && qt <= qhiw) {
-        // doc_start is monotone: the tile's last query has the largest
-        const int dlast = __builtin_amdgcn_readfirstlane(((const int*)(smem + cur * BUF + 4 * 8192 + 512))[AQ - 1]);
-        if (dlast > k0w) compute(smem + cur * BUF, std::integral_constant<int, 2>{});
-        else if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
-        else compute(smem + cur * BUF, std::integral_constant<int, 1>{});
-      }
-    } else if constexpr (BIDIR) {
-      if (k0w < L) {  // a wave past L only stages its pieces of the tiles
-        // the query tiles below qfull are full; kept in a VGPR for a per-wave branch, as kd in attn_fwd_dma_kernel
-        // (306 -> 234 VGPRs: two waves per SIMD)
-        int qfull = L / AQ;
-        asm volatile("" : "+v"(qfull));
-        if (qt < qfull) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
-        else compute(smem + cur * BUF, std::integral_constant<int, 3>{});
-      }
-    } else if (live && qt >= qtw) {
-      if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
-      else compute(smem + cur * BUF, std::integral_constant<int, 1>{});
-    }
-    if (more) {
-      attn_vm_drain();
-      stash(cur ^ 1);
-    }
-    __syncthreads();
-  };
-  for (int qt = qs; qt < qend; qt += 2) {
-    step(qt, std::integral_constant<int, 0>{});
-    if (qt + 1 < qend) step(qt + 1, std::integral_constant<int, 1>{});
-  }
-  if (!live) return;
-  // dK, dV (bf16) -> dqkv[b, key, 1|2, h, :]
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    uint16_t* dkb = dqkv + (int64_t)b * T * RS + (int64_t)(k0w + 16 * r + li) * RS + H * AD + (int64_t)h * AD;
-    uint16_t* dvb = dkb + H * AD;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      u32x2 a, c;
-      a[0] = pack_bf2(dk[r][d][0] * scale, dk[r][d][1] * scale);
-      a[1] = pack_bf2(dk[r][d][2] * scale, dk[r][d][3] * scale);
-      if constexpr (DROP) dv[r][d] *= dscale;
-      c[0] = pack_bf2(dv[r][d][0], dv[r][d][1]);
-      c[1] = pack_bf2(dv[r][d][2], dv[r][d][3]);
-      if constexpr (BIDIR) {
-        const bool vis = k0w + 16 * r + li < L;
-        a = vis ? a : u32x2{0u, 0u};
-        c = vis ? c : u32x2{0u, 0u};
-      }
-      *(u32x2*)(dkb + 16 * d + 4 * g) = a;
-      *(u32x2*)(dvb + 16 * d + 4 * g) = c;
-    }
-  }
+  constexpr bool GQA = false;
+  [[maybe_unused]] const int Hkv = H;
+#include "attn_dma_dkv_body.h"
 }
+DPE_NO_PK_F32_BEGIN
+template <bool PACKED>
+__global__ __launch_bounds__(256) void attn_bwd_gqa_kernel(
+    const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse2,
+    const float* __restrict__ delta, uint16_t* __restrict__ dqkv, int B, int T, int Hq, int Hkv, float sl2, float scale,
+    const int* __restrict__ doc_start, const int* __restrict__ doc_end) {
+  constexpr bool GQA = true, DROP = false, BIDIR = false;
+  const int H = Hq;
+  [[maybe_unused]] const AttnDrop dr{};
+  [[maybe_unused]] const int L = 0;
+#include "attn_dma_dkv_body.h"
+}
+DPE_NO_PK_F32_END
 
 // dQ: the forward's structure with the query on the lane (one workgroup = 128 queries,
 // 4 waves x 32 queries, looping over key tiles <= the query tile).  S^T = K.Q^T and
@@ -1262,6 +779,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const uint16_t* __rest
 // DROP: dS = P (M s dP - delta) with the forward's mask words; the dP chain starts from 0.
 // BIDIR: the forward's walk (attn_fwd_dma_kernel) -- key tiles 0 .. ceil(L / 64) - 1, the last one with P and dS of the
 // keys >= L selected to 0 after the exp2.  dQ rows >= L are exact zeros and delta rows >= L are 0.0f.
+// GQA: the forward's addressing (attn_fwd_dma_body) -- K / V of head h / (Hq / Hkv), the grouped row stride.
 template <bool PACKED, bool DROP, bool BIDIR = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAVES))) void attn_bwd_dq_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o,
                                                           const uint16_t* __restrict__ dout,
@@ -1269,217 +787,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
                                                           uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
                                                           float scale, const int* __restrict__ doc_start, AttnDrop dr,
                                                           int L) {
-  static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
-  // per buffer: K (two d-halves, K-contig) 8K | V (same) 8K | K permuted-row image 8K
-  constexpr int KI = 0, VI = 2 * AKV * 64, KP = 4 * AKV * 64, STG = KP + AKV * 128;
-  __shared__ __attribute__((aligned(16))) char smem[2 * STG];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
-  const int nq = (T + FQ - 1) / FQ, BH = B * H;
-  const int qt = nq - 1 - (int)(blockIdx.x / BH);  // heaviest query tiles first
-  const int bh = blockIdx.x % BH, b = bh / H, h = bh % H;
-  const int64_t RS = 3LL * H * AD;
-  const int64_t ORS = (int64_t)H * AD;
-  const uint16_t* qb = qkv + (int64_t)b * T * RS + (int64_t)h * AD;
-  const uint16_t* kb = qb + H * AD;
-  const uint16_t* vb = qb + 2 * H * AD;
-  const int q0w = qt * FQ + 32 * w;
-  const bool live = q0w < T;
-  const int ktw = live ? (q0w + 31) / AKV : -1;
-  int kd = BIDIR ? L / AKV : (q0w + 1) / AKV;  // key tiles below kd need no mask (bidirectional: are full)
-  if constexpr (BIDIR) asm volatile("" : "+v"(kd));  // a per-wave branch, as in attn_fwd_dma_kernel (222 -> 195 VGPRs)
-  const int nkt = BIDIR ? (L + AKV - 1) / AKV : min((qt * FQ + FQ - 1) / AKV, T / AKV - 1) + 1;
-  if constexpr (BIDIR) {
-    if (qt * FQ >= L) {  // every query of the workgroup is padding (workgroup-uniform: no barrier is left behind)
-      if (live) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const int myq = q0w + 16 * r + li;
-          uint16_t* dq = dqkv + ((int64_t)b * T + myq) * RS + (int64_t)h * AD;
-#pragma unroll
-          for (int d = 0; d < 4; ++d) *(u32x2*)(dq + 16 * d + 4 * g) = u32x2{0u, 0u};
-          if (g == 0) delta[(int64_t)bh * T + myq] = 0.f;
-        }
-      }
-      return;
-    }
-  }
-
-  // the wave's Q / dO rows as B operands; delta = rowsum(dO * O) from the same lanes (the
-  // lane's 16 d-values, then the 4-group permlane reduce), published for the dK/dV kernel
-  bf16x8 qf[2][2], of[2][2];
-  float lq[2], ndl[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const int myq = live ? q0w + 16 * r + li : 0;
-    float dot = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int64_t oo = ((int64_t)b * T + myq) * ORS + (int64_t)h * AD + 32 * kk + 8 * g;
-      const u32x4 dov = *(const u32x4*)(dout + oo);
-      qf[r][kk] = __builtin_bit_cast(bf16x8, *(const u32x4*)(qb + (int64_t)myq * RS + 32 * kk + 8 * g));
-      of[r][kk] = __builtin_bit_cast(bf16x8, dov);
-      float fa[8], fb[8];
-      unpack8(dov, fa);
-      unpack8(*(const u32x4*)(o + oo), fb);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) dot = fmaf(fa[e], fb[e], dot);
-    }
-    dot = rowsum4(dot);
-    if constexpr (BIDIR) dot = myq < L ? dot : 0.f;
-    if (live && g == 0) delta[(int64_t)bh * T + myq] = dot;
-    lq[r] = lse2[(int64_t)bh * T + myq];
-    ndl[r] = -dot;
-  }
-
-  // packed: first key tile of the workgroup / of the wave, first key no lower mask is needed from, the lane's bounds
-  int kt0 = 0, klo = 0, dshi = 0, ds[2] = {0, 0};
-  if constexpr (PACKED) {
-    const int* dsb = doc_start + (int64_t)b * T;
-    kt0 = min(max(__builtin_amdgcn_readfirstlane(dsb[qt * FQ]) / AKV, 0), nkt - 1);
-    if (live) {
-      klo = __builtin_amdgcn_readfirstlane(dsb[q0w]) / AKV;
-      dshi = __builtin_amdgcn_readfirstlane(dsb[q0w + 31]);
-      ds[0] = dsb[q0w + li];
-      ds[1] = dsb[q0w + 16 + li];
-    }
-  }
-
-  // the sequence's qkv rows from K of head h on: one buffer resource, tile advance in soffset
-  // dropout: the forward's counters (attn_fwd_dma_kernel)
-  [[maybe_unused]] uint64_t dseed = 0, dctr[2] = {0, 0};
-  [[maybe_unused]] float dscale = 1.f;
-  if constexpr (DROP) {
-    const uint64_t n4 = (uint64_t)(T >> 2);
-    dseed = (uint64_t)dr.rng[0];
-    dscale = 256.f / (float)(256u - dr.thr);
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-      dctr[r] = (uint64_t)dr.rng[1] + ((uint64_t)bh * n4 + (uint64_t)((q0w + 16 * r + li) >> 2)) * n4 + (uint64_t)(4 * (li & 3) + g);
-  }
-  const __amdgpu_buffer_rsrc_t rkv =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(kb), (short)0, (int)(T * RS * 2), 0x00020000);
-  uint32_t voff[6];  // piece w + 4 i of the 24 KiB image set: [K halves | V halves | K permuted-row]
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const int oo = ((w + 4 * i) * 1024 + lane * 16) & 8191;
-    int row, dc;
-    if (i < 4) {  // (dc >> 2) * 4096 + kimg(row, dc & 3)
-      const int o2 = oo & 4095;
-      row = o2 >> 6;
-      dc = 4 * (oo >> 12) + (((o2 >> 4) & 3) ^ ((0x78 >> (((row >> 2) & 3) << 1)) & 3));
-    } else {      // pimg(row, dc)
-      row = oo >> 7;
-      dc = ((oo >> 4) & 7) ^ (((row >> 1) & 3) << 1);
-    }
-    voff[i] = (uint32_t)(((int64_t)row * RS + ((i & 6) == 2 ? H * AD : 0) + dc * 8) * 2);
-  }
-  auto dma_tile = [&](int kt, int buf) {
-    char* base = smem + buf * STG;
-    const uint32_t so = (uint32_t)((int64_t)kt * AKV * RS * 2);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) attn_dma16(rkv, base + (w + 4 * i) * 1024, voff[i], so);
-  };
-
-  f32x4 acc[2][4];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int d = 0; d < 4; ++d) acc[r][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-  dma_tile(kt0, 0);
-  attn_vm_drain();
-  __syncthreads();
-  // the tile loop unrolled by two: the LDS buffer of each step is a compile-time constant, so every
-  // fragment address is a hoisted per-lane offset plus an immediate
-  auto step = [&](int kt, auto bufc) {
-    constexpr int cur = decltype(bufc)::value;
-    const bool more = kt + 1 < nkt;
-    if (more) dma_tile(kt + 1, cur ^ 1);  // cur ^ 1 last read before the previous barrier
-    // maskc: 0 no mask, 1 causal mask, 2 (packed only) causal and document-start mask, 3 (bidirectional only) key < L
-    auto compute = [&](const char* s, auto maskc) __attribute__((always_inline)) {
-      constexpr int MK = decltype(maskc)::value;
-      constexpr bool MASK = MK == 1;
-      f32x4 sc[2][4], dp[2][4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        const bf16x8 k0 = kfrag64(s + KI, 16 * nt), k1 = kfrag64(s + KI + AKV * 64, 16 * nt);
-        const bf16x8 v0 = kfrag64(s + VI, 16 * nt), v1 = kfrag64(s + VI + AKV * 64, 16 * nt);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          sc[r][nt] = MFMA(k1, qf[r][1], MFMA(k0, qf[r][0], (f32x4{0.f, 0.f, 0.f, 0.f})));
-          const float c0 = DROP ? 0.f : ndl[r];
-          dp[r][nt] = MFMA(v1, of[r][1], MFMA(v0, of[r][0], (f32x4{c0, c0, c0, c0})));
-        }
-      }
-      bf16x8 dd[2][2];
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int myq = q0w + 16 * r + li;
-        [[maybe_unused]] uint32_t dw[4];
-        if constexpr (DROP) drop_words_q(dw, dseed, dctr[r], (uint32_t)kt * (AKV / 4), dr.stream, li & 3);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float p = __builtin_amdgcn_exp2f(fmaf(sc[r][nt][e], sl2, -lq[r]));
-            if constexpr (MASK)
-              if (kt * AKV + 16 * nt + 4 * g + e > myq) p = 0.f;
-            if constexpr (MK == 2) {
-              const int key = kt * AKV + 16 * nt + 4 * g + e;
-              p = ((key > myq) | (key < ds[r])) ? 0.f : p;
-            }
-            if constexpr (DROP)  // dS^T = P (M s dP^T - delta); dP^T started from 0
-              dp[r][nt][e] = p * fmaf(dp[r][nt][e], drop_keep(dw[nt], e, dr.thr) ? dscale : 0.f, ndl[r]);
-            else if constexpr (MK == 3)  // a padding key: dS is 0 by select, whatever its K / V rows hold
-              dp[r][nt][e] = (kt * AKV + 16 * nt + 4 * g + e < L) ? p * dp[r][nt][e] : 0.f;
-            else
-              dp[r][nt][e] = p * dp[r][nt][e];  // dS^T (unscaled); dP^T started from -delta
-          }
-        dd[r][0] = pack_frag(dp[r][0], dp[r][1]);
-        dd[r][1] = pack_frag(dp[r][2], dp[r][3]);
-      }
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const bf16x8 a0 = trfrag(s + KP, 0, 16 * d), a1 = trfrag(s + KP, 32, 16 * d);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) acc[r][d] = MFMA(a1, dd[r][1], MFMA(a0, dd[r][0], acc[r][d]));
-      }
-    };
-    if constexpr (PACKED) {
-      if (kt >= klo && kt <= ktw) {
-        if (kt * AKV < dshi) compute(smem + cur * STG, std::integral_constant<int, 2>{});
-        else if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
-        else compute(smem + cur * STG, std::integral_constant<int, 1>{});
-      }
-    } else if constexpr (BIDIR) {
-      if (q0w < L) {  // a wave past L only stages its pieces of the tiles
-        if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
-        else compute(smem + cur * STG, std::integral_constant<int, 3>{});
-      }
-    } else {
-      if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});
-      else if (kt <= ktw) compute(smem + cur * STG, std::integral_constant<int, 1>{});
-    }
-    if (more) attn_vm_drain();
-    __syncthreads();
-  };
-  for (int kt = kt0; kt < nkt; kt += 2) {
-    step(kt, std::integral_constant<int, 0>{});
-    if (kt + 1 < nkt) step(kt + 1, std::integral_constant<int, 1>{});
-  }
-  if (!live) return;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    uint16_t* o = dqkv + ((int64_t)b * T + q0w + 16 * r + li) * RS + (int64_t)h * AD;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      u32x2 pk;
-      pk[0] = pack_bf2(acc[r][d][0] * scale, acc[r][d][1] * scale);
-      pk[1] = pack_bf2(acc[r][d][2] * scale, acc[r][d][3] * scale);
-      if constexpr (BIDIR) pk = q0w + 16 * r + li < L ? pk : u32x2{0u, 0u};
-      *(u32x2*)(o + 16 * d + 4 * g) = pk;
-    }
-  }
+  constexpr bool GQA = false;
+  [[maybe_unused]] const int Hkv = H;
+#include "attn_dma_dq_body.h"
 }
+DPE_NO_PK_F32_BEGIN
+template <bool PACKED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAVES))) void attn_bwd_dq_gqa_kernel(
+    const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o, const uint16_t* __restrict__ dout,
+    const float* __restrict__ lse2, float* __restrict__ delta, uint16_t* __restrict__ dqkv, int B, int T, int Hq, int Hkv,
+    float sl2, float scale, const int* __restrict__ doc_start) {
+  constexpr bool GQA = true, DROP = false, BIDIR = false;
+  const int H = Hq;
+  [[maybe_unused]] const AttnDrop dr{};
+  [[maybe_unused]] const int L = 0;
+#include "attn_dma_dq_body.h"
+}
+DPE_NO_PK_F32_END
 
 }  // namespace dpe
 
@@ -1625,5 +949,48 @@ extern "C" int dpe_attn_bwd_bidir(const uint16_t* qkv, const uint16_t* out, cons
                      H, sl2, scale, (const int*)nullptr, AttnDrop{}, seq_len);
   hipLaunchKernelGGL((attn_bwd_dma_kernel<false, false, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2,
                      scale, (const int*)nullptr, (const int*)nullptr, AttnDrop{}, seq_len);
+  return 0;
+}
+
+// Grouped-query attention (causal; doc_start / doc_end as above): qkv [B, T, Hq + 2 Hkv, 64], out [B, T, Hq, 64], lse and
+// delta [B, Hq, T], Hq % Hkv == 0 (Hkv == Hq is today's layout).  LDS-DMA kernels only, no dropout: a shape or switch
+// that would take the register-staged kernels is an error, as for packed documents.
+static bool gqa_ok(int T, int Hq, int Hkv, int D, const int32_t* doc_start, const int32_t* doc_end) {
+  if (D != AD || T < AKV || T % AKV != 0 || Hkv < 1 || Hq < Hkv || Hq % Hkv != 0) return false;
+  if ((doc_start != nullptr) != (doc_end != nullptr)) return false;
+  // one sequence's qkv rows must fit the DMA kernels' 32-bit buffer range
+  return !g_attn_staged && (int64_t)T * (Hq + 2 * Hkv) * AD * 2 < (1LL << 31);
+}
+
+extern "C" int dpe_attn_fwd_gqa(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int Hq, int Hkv, int D,
+                                float scale, const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
+  if (!gqa_ok(T, Hq, Hkv, D, doc_start, doc_end)) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  const dim3 grid(B * Hq * ((T + FQ - 1) / FQ));
+  if (doc_start)
+    hipLaunchKernelGGL(attn_fwd_gqa_kernel<true>, grid, dim3(256), 0, st, qkv, out, lse, B, T, Hq, Hkv, sl2, doc_start);
+  else
+    hipLaunchKernelGGL(attn_fwd_gqa_kernel<false>, grid, dim3(256), 0, st, qkv, out, lse, B, T, Hq, Hkv, sl2, (const int*)nullptr);
+  return 0;
+}
+
+extern "C" int dpe_attn_bwd_gqa(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
+                                float* delta, uint16_t* dqkv, int B, int T, int Hq, int Hkv, int D, float scale,
+                                const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
+  if (!gqa_ok(T, Hq, Hkv, D, doc_start, doc_end)) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  // dQ over the query heads first (it also writes delta); dK / dV over the KV heads, each walking its group
+  const dim3 gq(B * Hq * ((T + FQ - 1) / FQ)), gk(B * Hkv * ((T + BKW - 1) / BKW));
+  if (doc_start) {
+    hipLaunchKernelGGL(attn_bwd_dq_gqa_kernel<true>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2,
+                       scale, doc_start);
+    hipLaunchKernelGGL(attn_bwd_gqa_kernel<true>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2, scale,
+                       doc_start, doc_end);
+  } else {
+    hipLaunchKernelGGL(attn_bwd_dq_gqa_kernel<false>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2,
+                       scale, (const int*)nullptr);
+    hipLaunchKernelGGL(attn_bwd_gqa_kernel<false>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2, scale,
+                       (const int*)nullptr, (const int*)nullptr);
+  }
   return 0;
 }

@@ -6,6 +6,12 @@
 
 #define DPE_HOST_DEVICE __host__ __device__ __forceinline__
 #define DPE_DEVICE __device__ __forceinline__
+// Between BEGIN and END: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) in the code of the functions defined
+// there, lambdas included -- the per-function form of the -packed-fp32-ops target feature that dwconv.hip takes
+// file-wide (_build.py FILE_FLAGS), for new kernels in a file whose other kernels keep the code they have.
+#define DPE_NO_PK_F32_BEGIN \
+  _Pragma("clang attribute push(__attribute__((target(\"no-packed-fp32-ops\"))), apply_to = function)")
+#define DPE_NO_PK_F32_END _Pragma("clang attribute pop")
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));

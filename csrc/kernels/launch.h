@@ -191,6 +191,13 @@ int dpe_attn_fwd_bidir(const uint16_t* qkv, uint16_t* out, float* lse, int B, in
                        hipStream_t st);
 int dpe_attn_bwd_bidir(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
                        uint16_t* dqkv, int B, int T, int H, int D, float scale, int seq_len, hipStream_t st);
+// grouped-query attention (causal; LDS-DMA kernels only, no dropout): qkv [B, T, Hq + 2 Hkv, 64], Hq % Hkv == 0;
+// out [B, T, Hq, 64], lse / delta [B, Hq, T]; doc_start / doc_end as above
+int dpe_attn_fwd_gqa(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int Hq, int Hkv, int D, float scale,
+                     const int32_t* doc_start, const int32_t* doc_end, hipStream_t st);
+int dpe_attn_bwd_gqa(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
+                     uint16_t* dqkv, int B, int T, int Hq, int Hkv, int D, float scale, const int32_t* doc_start,
+                     const int32_t* doc_end, hipStream_t st);
 // ---- decode.hip
 // one query per (b, h) against the head-major cache kc / vc [B, H, Tmax, 64]; qkv_step [B, 3, H, 64]; len int32 [B]
 // (clamped into [0, Tmax - 1]); S key splits (ws: dpe_attn_decode_ws_floats fp32, unused for S = 1); out [B, H * 64]

@@ -983,6 +983,43 @@ class _AttnFn(Function):
         return dqkv, None, None, None, None, None, None, None
 
 
+class _GqaAttnFn(Function):
+    """Grouped-query causal attention on the GQA kernels: qkv [B, T, Hq + 2 Hkv, 64], optional packed documents."""
+
+    @staticmethod
+    def forward(ctx, qkv, H: int, Hkv: int, scale: float, doc_start=None, doc_end=None):
+        out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True, doc_start=doc_start, doc_end=doc_end, n_kv_head=Hkv)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.args = H, Hkv, scale, doc_start, doc_end
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        H, Hkv, scale, ds, de = ctx.args
+        dqkv = ext().attn_bwd(qkv.contiguous(), out, dout.contiguous().to(torch.bfloat16), lse, H, scale, True,
+                              doc_start=ds, doc_end=de, n_kv_head=Hkv)
+        return dqkv, None, None, None, None, None
+
+
+def _gqa_attention(qkv, n_head: int, n_kv_head: int, doc_bounds):
+    """causal_attention with n_kv_head: qkv [B, T, (Hq + 2 Hkv) * D]."""
+    B, T, w = qkv.shape
+    if n_kv_head < 1 or n_head % n_kv_head:
+        raise ValueError(f"n_head ({n_head}) must be a multiple of n_kv_head ({n_kv_head})")
+    D = w // (n_head + 2 * n_kv_head)
+    scale = 1.0 / math.sqrt(D)
+    ds, de = (doc_bounds[0], doc_bounds[1]) if doc_bounds is not None else (None, None)
+    if qkv.is_cuda and attn_kernel_ok(T, D):
+        out = _GqaAttnFn.apply(qkv.reshape(B, T, n_head + 2 * n_kv_head, D), n_head, n_kv_head, scale, ds, de)
+        return out.reshape(B, T, n_head * D)
+    # off the GPU and for other shapes: K / V expanded to one head per query head, then the explicit softmax
+    q, k, v = qkv.reshape(B, T, n_head + 2 * n_kv_head, D).split([n_head, n_kv_head, n_kv_head], dim=2)
+    g = n_head // n_kv_head
+    qkv5 = torch.stack([q, k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)], dim=2)
+    return _causal_attention_torch(qkv5, scale, ds).reshape(B, T, n_head * D)
+
+
 def attn_kernel_ok(T: int, D: int) -> bool:
     """The shapes the flash-attention kernels take (csrc/kernels/attn.hip): head dim 64, whole 64-key tiles."""
     return D == 64 and T % 64 == 0
@@ -1007,12 +1044,19 @@ def _causal_attention_torch(qkv5, scale: float, doc_start=None, dropout_p: float
     return o.transpose(1, 2).to(qkv5.dtype)  # [B, T, H, D]
 
 
-def causal_attention(qkv, n_head: int, doc_bounds=None, dropout_p: float = 0.0, rng=None, stream: int = 0):
+def causal_attention(qkv, n_head: int, doc_bounds=None, dropout_p: float = 0.0, rng=None, stream: int = 0,
+                     n_kv_head: Optional[int] = None):
     """qkv: [B, T, 3*H*D] -> [B, T, H*D] causal softmax attention.  ``doc_bounds`` (the tuple doc_bounds()
     returns): attention stays inside each packed document.  ``dropout_p`` > 0 (training; the caller decides):
     dropout on the attention probabilities -- inside the flash kernels at the rate attn_dropout_rate(dropout_p),
     with the mask drawn from ``rng`` (a DropoutState snapshot, default: a fresh one, after which the state is
-    advanced) and ``stream``; off the GPU or for other shapes an explicit softmax with F.dropout on P."""
+    advanced) and ``stream``; off the GPU or for other shapes an explicit softmax with F.dropout on P.
+    ``n_kv_head``: grouped-query attention -- qkv is [B, T, (H + 2 * n_kv_head) * D], the H query heads, then the key
+    heads, then the value heads, and query head h attends to K / V head h // (H // n_kv_head); no dropout."""
+    if n_kv_head is not None:
+        if dropout_p != 0.0:
+            raise ValueError("causal_attention: n_kv_head has no attention dropout")
+        return _gqa_attention(qkv, n_head, n_kv_head, doc_bounds)
     B, T, three_hd = qkv.shape
     D = three_hd // (3 * n_head)
     scale = 1.0 / math.sqrt(D)
