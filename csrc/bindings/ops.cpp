@@ -4,8 +4,11 @@
 // HIP stream, so the ops compose with the caching allocator and hipGraph
 // capture (no host sync, no hipMalloc inside).
 #include <algorithm>
+#include <string>
+#include <tuple>
 #include <vector>
 
+#include "../kernels/attn.h"
 #include "ops_common.h"
 
 namespace dpe_ops {
@@ -573,7 +576,11 @@ void layernorm_bwd_finalize_group(const std::vector<Tensor>& parts, const std::v
 // qkv: [B, T, 3, H, D] bf16 -> out [B, T, H, D] bf16, lse [B, H, T] f32 (both optionally caller-allocated).
 // doc_start / doc_end (int32 [B, T], together): the packed-document mask doc_start[b, i] <= j <= i.
 // dropout_p > 0: dropout on P inside the kernels at the 8-bit rate thr / 256, thr = clamp(round(256 p), 1, 255); rng is
-// the device int64[2] (seed, offset) the kernels read, stream the call site (Philox counter_lo).  0 = today's kernels.
+// the device int64[2] (seed, offset) the kernels read, stream the call site (Philox counter_lo).  0 = no dropout.
+// causal = false: bidirectional attention over the first seq_len rows (0 = T).
+// n_kv_head > 0: grouped-query attention.  qkv is [B, T, H + 2 * n_kv_head, D] (H query heads, then the key heads, then the
+// value heads); 0 = one K / V head per query head in the [B, T, 3, H, D] layout.
+// Which of these combine, and on which kernels: dpe_attn_route (csrc/kernels/attn.hip).
 const int64_t* drop_rng(double p, const c10::optional<Tensor>& rng, int64_t stream, const Tensor& like, uint32_t* thr) {
   TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout_p must be in [0, 1), got ", p);
   TORCH_CHECK(stream >= 0 && stream <= 0xffffffffLL, "attn: stream must fit 32 bits");
@@ -587,65 +594,61 @@ const int64_t* drop_rng(double p, const c10::optional<Tensor>& rng, int64_t stre
   return (const int64_t*)rng->data_ptr();
 }
 
-// causal = false: bidirectional attention over the first seq_len rows (0 = T); no doc_start, no dropout.
-void bidir_args(const c10::optional<Tensor>& doc_start, const c10::optional<Tensor>& doc_end, double dropout_p,
-                const c10::optional<Tensor>& rng, int64_t seq_len, int64_t T) {
-  TORCH_CHECK(!has(doc_start) && !has(doc_end), "attn: causal=False takes no doc_start / doc_end");
-  TORCH_CHECK(dropout_p == 0.0 && !has(rng), "attn: causal=False takes no dropout arguments");
-  TORCH_CHECK(seq_len >= 0 && seq_len <= T, "attn: seq_len must be in [1, T] (0 = T), got ", seq_len);
-}
+// The mode arguments attn_fwd and attn_bwd share.
+struct AttnMode {
+  int64_t H;
+  double scale;
+  bool causal;
+  const c10::optional<Tensor>&doc_start, &doc_end;
+  double dropout_p;
+  const c10::optional<Tensor>& rng;
+  int64_t stream, seq_len, n_kv_head;
+};
 
-// n_kv_head > 0: grouped-query attention.  qkv is [B, T, H + 2 * n_kv_head, D] (H query heads, then the key heads, then the
-// value heads), H % n_kv_head == 0; causal only, with or without doc_start / doc_end; no dropout, no seq_len, LDS-DMA
-// kernels only.  0 = one K / V head per query head in the [B, T, 3, H, D] layout: the paths above.
-void gqa_args(int64_t H, int64_t n_kv_head, bool causal, double dropout_p, const c10::optional<Tensor>& rng, int64_t seq_len) {
-  TORCH_CHECK(n_kv_head >= 1 && H % n_kv_head == 0, "attn: H (", H, ") must be a multiple of n_kv_head (", n_kv_head, ")");
-  TORCH_CHECK(causal && seq_len == 0, "attn: n_kv_head goes with causal=True and no seq_len");
-  TORCH_CHECK(dropout_p == 0.0 && !has(rng), "attn: n_kv_head takes no dropout arguments");
+// The AttnArgs of a call: the forward's (dout, dqkv null) or the backward's (delta is the caller's to set).  The kernels
+// index every tensor by B, T, H, so every tensor is checked, the same way in every mode and both directions.
+dpe::AttnArgs attn_args(const char* fn, const AttnMode& m, const Tensor& qkv, const Tensor& out, const Tensor& lse,
+                        const Tensor* dout, const Tensor* dqkv) {
+  CHECK_GPU(qkv);
+  TORCH_CHECK(qkv.dim() >= 3, fn, ": qkv must be [B,T,3,H,D] ([B,T,H+2*n_kv_head,D] with n_kv_head)");
+  const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1), H = m.H;
+  dpe::AttnArgs a{};
+  a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)m.n_kv_head, a.D = (int)D;
+  a.scale = (float)m.scale, a.causal = m.causal, a.seq_len = (int)m.seq_len, a.stream = (uint32_t)m.stream;
+  TORCH_CHECK(has(m.doc_start) == has(m.doc_end), fn, ": doc_start and doc_end go together");
+  a.doc_start = i32_opt(m.doc_start, B * T, qkv, "attn: doc_start");
+  a.doc_end = i32_opt(m.doc_end, B * T, qkv, "attn: doc_end");
+  drop_rng(m.dropout_p, m.rng, m.stream, qkv, &a.thr);
+  // an rng without dropout is never read: the causal kernels ignore it, the other modes refuse it (dpe_attn_route)
+  a.rng = has(m.rng) ? (const int64_t*)m.rng->data_ptr() : nullptr;
+  const char* why = "";
+  TORCH_CHECK(dpe_attn_route(a, &why) != dpe::AR_NONE, why, " (", fn, ": T=", T, ", H=", H, ", n_kv_head=", m.n_kv_head,
+              ", D=", D, ", seq_len=", m.seq_len, ")");
+  auto tensor = [&](const Tensor& t, at::ScalarType ty, int64_t n, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == n,
+                fn, ": ", what, ", contiguous and on qkv's device");
+    return t.data_ptr();
+  };
+  a.qkv = (const uint16_t*)tensor(qkv, at::kBFloat16, B * T * (a.Hkv ? H + 2 * a.Hkv : 3 * H) * D,
+                                  "qkv must be bf16 [B,T,3,H,D] ([B,T,H+2*n_kv_head,D] with n_kv_head)");
+  a.out = (uint16_t*)tensor(out, at::kBFloat16, B * T * H * D, "out must be bf16 [B,T,H,D]");
+  a.lse = (float*)tensor(lse, at::kFloat, B * H * T, "lse must be f32 [B,H,T]");
+  if (dout) a.dout = (const uint16_t*)tensor(*dout, at::kBFloat16, B * T * H * D, "dout must be bf16 [B,T,H,D]");
+  if (dqkv) a.dqkv = (uint16_t*)tensor(*dqkv, at::kBFloat16, qkv.numel(), "dqkv must be bf16 of qkv's size");
+  return a;
 }
 
 std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal, const c10::optional<Tensor>& out_,
                              const c10::optional<Tensor>& lse_, const c10::optional<Tensor>& doc_start,
                              const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng,
                              int64_t stream, int64_t seq_len, int64_t n_kv_head) {
-  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_CONTIG(qkv);
+  TORCH_CHECK(qkv.dim() >= 3, "attn_fwd: qkv must be [B,T,3,H,D] ([B,T,H+2*n_kv_head,D] with n_kv_head)");
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
-  if (n_kv_head != 0) gqa_args(H, n_kv_head, causal, dropout_p, rng, seq_len);
-  TORCH_CHECK(qkv.numel() == B * T * (n_kv_head ? H + 2 * n_kv_head : 3 * H) * D,
-              "attn: qkv must be [B,T,3,H,D] ([B,T,H+2*n_kv_head,D] with n_kv_head)");
-  TORCH_CHECK(D == 64, "attn: head dim 64 supported");
   Tensor out = has(out_) ? *out_ : at::empty({B, T, H, D}, qkv.options());
   Tensor lse = has(lse_) ? *lse_ : at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
-  CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out); CHECK_GPU(lse); CHECK_F32(lse); CHECK_CONTIG(lse);
-  TORCH_CHECK(out.numel() == B * T * H * D && lse.numel() == B * H * T, "attn_fwd: out is [B,T,H,D], lse [B,H,T]");
-  TORCH_CHECK(has(doc_start) == has(doc_end), "attn_fwd: doc_start and doc_end go together");
-  if (n_kv_head != 0) {
-    CHECK_RC(dpe_attn_fwd_gqa(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)n_kv_head, (int)D, (float)scale,
-                              i32_opt(doc_start, B * T, qkv, "attn_fwd: doc_start"),
-                              i32_opt(doc_end, B * T, qkv, "attn_fwd: doc_end"), cur_stream()),
-             "attn_fwd (n_kv_head: LDS-DMA kernels only)");
-    return {out, lse};
-  }
-  if (!causal) {
-    bidir_args(doc_start, doc_end, dropout_p, rng, seq_len, T);
-    CHECK_RC(dpe_attn_fwd_bidir(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale,
-                                (int)(seq_len ? seq_len : T), cur_stream()),
-             "attn_fwd (bidirectional: LDS-DMA kernels only)");
-    return {out, lse};
-  }
-  TORCH_CHECK(seq_len == 0, "attn: seq_len goes with causal=False");
-  uint32_t thr;
-  if (const int64_t* rp = drop_rng(dropout_p, rng, stream, qkv, &thr)) {
-    CHECK_RC(dpe_attn_fwd_drop(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal,
-                               i32_opt(doc_start, B * T, qkv, "attn_fwd: doc_start"),
-                               i32_opt(doc_end, B * T, qkv, "attn_fwd: doc_end"), rp, (uint32_t)stream, thr, cur_stream()),
-             "attn_fwd (dropout: LDS-DMA kernels only)");
-    return {out, lse};
-  }
-  CHECK_RC(dpe_attn_fwd(bp(qkv), bpm(out), fp(lse), (int)B, (int)T, (int)H, (int)D, (float)scale, causal,
-                        i32_opt(doc_start, B * T, qkv, "attn_fwd: doc_start"),
-                        i32_opt(doc_end, B * T, qkv, "attn_fwd: doc_end"), cur_stream()),
-           "attn_fwd");
+  const dpe::AttnArgs a = attn_args("attn_fwd", {H, scale, causal, doc_start, doc_end, dropout_p, rng, stream, seq_len, n_kv_head},
+                                    qkv, out, lse, nullptr, nullptr);
+  CHECK_RC(dpe_attn_fwd(a, cur_stream()), "attn_fwd");
   return {out, lse};
 }
 
@@ -653,47 +656,12 @@ Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const 
                 bool causal, const c10::optional<Tensor>& dqkv_, const c10::optional<Tensor>& doc_start,
                 const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng, int64_t stream,
                 int64_t seq_len, int64_t n_kv_head) {
-  CHECK_GPU(qkv); CHECK_BF16(dout); CHECK_CONTIG(dout); CHECK_CONTIG(out);
-  const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
-  if (n_kv_head != 0) {
-    gqa_args(H, n_kv_head, causal, dropout_p, rng, seq_len);
-    CHECK_BF16(qkv); CHECK_CONTIG(qkv); CHECK_GPU(out); CHECK_BF16(out); CHECK_GPU(dout); CHECK_GPU(lse); CHECK_F32(lse);
-    CHECK_CONTIG(lse);
-    TORCH_CHECK(D == 64 && qkv.numel() == B * T * (H + 2 * n_kv_head) * D, "attn_bwd: qkv must be [B,T,H+2*n_kv_head,64]");
-    TORCH_CHECK(out.numel() == B * T * H * D && dout.numel() == out.numel() && lse.numel() == B * H * T,
-                "attn_bwd: out and dout are [B,T,H,D], lse [B,H,T]");
-  }
   Tensor dqkv = has(dqkv_) ? *dqkv_ : at::empty_like(qkv);
-  CHECK_GPU(dqkv); CHECK_BF16(dqkv); CHECK_CONTIG(dqkv);
-  TORCH_CHECK(dqkv.numel() == qkv.numel(), "attn_bwd: dqkv must have qkv's size");
-  Tensor delta = at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
-  TORCH_CHECK(has(doc_start) == has(doc_end), "attn_bwd: doc_start and doc_end go together");
-  if (n_kv_head != 0) {
-    CHECK_RC(dpe_attn_bwd_gqa(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H,
-                              (int)n_kv_head, (int)D, (float)scale, i32_opt(doc_start, B * T, qkv, "attn_bwd: doc_start"),
-                              i32_opt(doc_end, B * T, qkv, "attn_bwd: doc_end"), cur_stream()),
-             "attn_bwd (n_kv_head: LDS-DMA kernels only)");
-    return dqkv;
-  }
-  if (!causal) {
-    bidir_args(doc_start, doc_end, dropout_p, rng, seq_len, T);
-    CHECK_RC(dpe_attn_bwd_bidir(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
-                                (float)scale, (int)(seq_len ? seq_len : T), cur_stream()),
-             "attn_bwd (bidirectional: LDS-DMA kernels only)");
-    return dqkv;
-  }
-  TORCH_CHECK(seq_len == 0, "attn: seq_len goes with causal=False");
-  uint32_t thr;
-  if (const int64_t* rp = drop_rng(dropout_p, rng, stream, qkv, &thr)) {
-    CHECK_RC(dpe_attn_bwd_drop(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
-                               (float)scale, causal, i32_opt(doc_start, B * T, qkv, "attn_bwd: doc_start"),
-                               i32_opt(doc_end, B * T, qkv, "attn_bwd: doc_end"), rp, (uint32_t)stream, thr, cur_stream()),
-             "attn_bwd (dropout: LDS-DMA kernels only)");
-    return dqkv;
-  }
-  CHECK_RC(dpe_attn_bwd(bp(qkv), bp(out), bp(dout), fp(lse), fp(delta), nullptr, bpm(dqkv), (int)B, (int)T, (int)H, (int)D,
-                        (float)scale, causal, i32_opt(doc_start, B * T, qkv, "attn_bwd: doc_start"),
-                        i32_opt(doc_end, B * T, qkv, "attn_bwd: doc_end"), cur_stream()), "attn_bwd");
+  dpe::AttnArgs a = attn_args("attn_bwd", {H, scale, causal, doc_start, doc_end, dropout_p, rng, stream, seq_len, n_kv_head},
+                              qkv, out, lse, &dout, &dqkv);
+  Tensor delta = at::empty({a.B, a.H, a.T}, qkv.options().dtype(at::kFloat));
+  a.delta = fp(delta);
+  CHECK_RC(dpe_attn_bwd(a, cur_stream()), "attn_bwd");
   return dqkv;
 }
 
@@ -791,6 +759,22 @@ void register_ops(pybind11::module& m) {
   m.def("set_attn_staged", [](bool on) { return dpe_set_attn_staged(on ? 1 : 0) != 0; }, py::arg("on"),
         "attention on the register-staged kernels instead of the LDS-DMA ones (test switch; default off); returns the "
         "previous setting");
+  m.def("attn_route", [](int64_t T, int64_t H, int64_t n_kv_head, int64_t D, bool causal, int64_t seq_len, bool packed,
+                         bool dropout) {
+          static const int64_t given[2] = {0, 0};  // stands for a tensor that was passed: the route only asks which are null
+          dpe::AttnArgs a{};
+          a.B = 1, a.T = (int)T, a.H = (int)H, a.Hkv = (int)n_kv_head, a.D = (int)D, a.causal = causal, a.seq_len = (int)seq_len;
+          a.doc_start = a.doc_end = packed ? (const int32_t*)given : nullptr;
+          a.rng = dropout ? given : nullptr;
+          a.thr = dropout ? 128 : 0;
+          static const char* const names[] = {"none", "staged", "dma", "gqa"};
+          const char* why = "";
+          const int r = dpe_attn_route(a, &why);
+          return std::make_tuple(std::string(names[r]), std::string(why));
+        }, py::arg("T"), py::arg("H"), py::arg("n_kv_head") = 0, py::arg("D") = 64, py::arg("causal") = true,
+        py::arg("seq_len") = 0, py::arg("packed") = false, py::arg("dropout") = false,
+        "the kernel family attn_fwd / attn_bwd would run for these arguments under the current set_attn_staged: "
+        "('none' | 'staged' | 'dma' | 'gqa', the reason when 'none'); no tensors, no GPU call");
   m.def("set_gemm_backend", [](int64_t mode) {
           TORCH_CHECK(mode == 1, "only the native MFMA GEMM backend exists (mode 1); the vendor-library arm was removed");
         }, "kept for API compatibility: 1 = native kernels (the only backend)");

@@ -42,6 +42,7 @@
 //   from before compiles to what it was.
 #include <type_traits>
 
+#include "attn.h"
 #include "common.h"
 #include "launch.h"
 
@@ -818,179 +819,108 @@ extern "C" int dpe_set_attn_staged(int on) {
   return was;
 }
 
-// doc_start / doc_end (both or neither; int32 [B, T]): the packed-document mask, LDS-DMA kernels only.
-extern "C" int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int causal,
-                            const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
-  if (D != AD || T % AKV != 0 || !causal) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  // one sequence's qkv rows must fit the DMA kernel's 32-bit buffer range
-  const bool dma = !g_attn_staged && (int64_t)T * 3 * H * AD * 2 < (1LL << 31);
-  const dim3 grid(B * H * ((T + FQ - 1) / FQ));
-  if (doc_start) {
-    if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
-    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, false>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, AttnDrop{}, 0);
+// The mode matrix (attn.h).  Packed documents, dropout, the bidirectional mask and grouped K / V heads exist on the
+// LDS-DMA kernels only: where those cannot run, such a call is an error and a plain causal one takes the register-staged
+// kernels.  Packed documents combine with dropout and with grouped heads; nothing else combines.
+extern "C" int dpe_attn_route(const AttnArgs& a, const char** why) {
+  const bool gqa = a.Hkv != 0, bidir = !a.causal, packed = a.doc_start || a.doc_end, drop = a.thr != 0;
+  // one sequence's qkv rows (dO has fewer) must fit the DMA kernels' 32-bit buffer range
+  const int64_t heads = gqa ? (int64_t)a.H + 2 * (int64_t)a.Hkv : 3 * (int64_t)a.H;
+  const bool dma = !g_attn_staged && (int64_t)a.T * heads * AD * 2 < (1LL << 31);
+  const char* no = nullptr;
+  if (gqa && (a.Hkv < 1 || a.H < a.Hkv || a.H % a.Hkv != 0)) no = "attn: H must be a multiple of n_kv_head";
+  else if (gqa && (bidir || a.seq_len != 0)) no = "attn: n_kv_head goes with causal=True and no seq_len";
+  else if (gqa && (drop || a.rng)) no = "attn: n_kv_head takes no dropout arguments";
+  else if (a.D != AD) no = "attn: head dim 64 supported";
+  else if (a.T % AKV != 0 || ((gqa || bidir) && a.T < AKV)) no = "attn: T must be a multiple of 64";
+  else if ((a.doc_start != nullptr) != (a.doc_end != nullptr)) no = "attn: doc_start and doc_end go together";
+  else if (bidir && packed) no = "attn: causal=False takes no doc_start / doc_end";
+  else if (bidir && (drop || a.rng)) no = "attn: causal=False takes no dropout arguments";
+  else if (bidir && (a.seq_len < 0 || a.seq_len > a.T)) no = "attn: seq_len must be in [1, T] (0 = T)";
+  else if (!bidir && a.seq_len != 0) no = "attn: seq_len goes with causal=False";
+  else if (drop && (!a.rng || a.thr > 255)) no = "attn: dropout needs rng and a threshold in [1, 255]";
+  else if (!dma && gqa) no = "attn: n_kv_head runs on the LDS-DMA kernels only (staged switch, or T * heads >= 2^31 bytes)";
+  else if (!dma && bidir) no = "attn: causal=False runs on the LDS-DMA kernels only (staged switch, or T * H >= 2^31 bytes)";
+  else if (!dma && drop) no = "attn: dropout runs on the LDS-DMA kernels only (staged switch, or T * H >= 2^31 bytes)";
+  else if (!dma && packed) no = "attn: doc_start runs on the LDS-DMA kernels only (staged switch, or T * H >= 2^31 bytes)";
+  if (no) {
+    if (why) *why = no;
+    return AR_NONE;
+  }
+  return gqa ? AR_GQA : dma ? AR_DMA : AR_STAGED;
+}
+
+// f(PACKED, DROP, BIDIR) with the call's three template switches as std::bool_constant values: the five combinations
+// the route lets through (GQA uses PACKED alone), so nothing else is instantiated.
+template <class F>
+static void with_mode(const AttnArgs& a, F f) {
+  constexpr std::true_type y{};
+  constexpr std::false_type n{};
+  const bool packed = a.doc_start != nullptr, drop = a.thr != 0;
+  if (!a.causal) f(n, n, y);
+  else if (packed && drop) f(y, y, n);
+  else if (packed) f(y, n, n);
+  else if (drop) f(n, y, n);
+  else f(n, n, n);
+}
+
+// What every launch of a call shares: scale * log2(e), the dropout block, the bidirectional key bound (0 = causal).
+struct AttnLaunch {
+  float sl2;
+  AttnDrop dr;
+  int L;
+  explicit AttnLaunch(const AttnArgs& a)
+      : sl2(a.scale * 1.4426950408889634f), dr(a.thr ? AttnDrop{a.rng, a.stream, a.thr} : AttnDrop{}),
+        L(a.causal ? 0 : a.seq_len ? a.seq_len : a.T) {}
+};
+
+extern "C" int dpe_attn_fwd(const AttnArgs& a, hipStream_t st) {
+  const int route = dpe_attn_route(a, nullptr);
+  if (route == AR_NONE) return -1;
+  const AttnLaunch l(a);
+  const dim3 grid(a.B * a.H * ((a.T + FQ - 1) / FQ)), blk(256);
+  if (route == AR_STAGED) {
+    hipLaunchKernelGGL(attn_fwd_kernel, grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T, a.H, l.sl2);
     return 0;
   }
-#ifdef DPE_ATTN_FWD_STAGED
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
-#else
-  if (dma)
-    hipLaunchKernelGGL((attn_fwd_dma_kernel<false, false>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, (const int*)nullptr,
-                       AttnDrop{}, 0);
-  else
-    hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2);
-#endif
+  with_mode(a, [&](auto P, auto Dr, auto Bi) {
+    constexpr bool PACKED = decltype(P)::value, DROP = decltype(Dr)::value, BIDIR = decltype(Bi)::value;
+    if (route == AR_GQA)
+      hipLaunchKernelGGL(attn_fwd_gqa_kernel<PACKED>, grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T, a.H, a.Hkv, l.sl2,
+                         a.doc_start);
+    else
+      hipLaunchKernelGGL((attn_fwd_dma_kernel<PACKED, DROP, BIDIR>), grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T, a.H,
+                         l.sl2, a.doc_start, l.dr, l.L);
+  });
   return 0;
 }
 
-extern "C" int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                            float* dq_acc, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal,
-                            const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
-  (void)dq_acc;  // dQ is not accumulated with atomics (attn_bwd_dq_kernel)
-  if (D != AD || T % AKV != 0 || !causal) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  // one sequence's qkv / dO rows must fit the DMA kernels' 32-bit buffer ranges
-  const bool dma = !g_attn_staged && (int64_t)T * 3 * H * AD * 2 < (1LL << 31);
-  const dim3 gq(B * H * ((T + FQ - 1) / FQ)), gk(B * H * ((T + BKW - 1) / BKW));
-  // dQ first: it also writes delta = rowsum(dO * O), which the dK/dV kernel reads
-  if (doc_start) {
-    if (!dma || !doc_end) return -1;  // the register-staged kernels have no packed variant
-    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<true, false>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, doc_start, AttnDrop{}, 0);
-    hipLaunchKernelGGL((attn_bwd_dma_kernel<true, false>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       doc_start, doc_end, AttnDrop{}, 0);
+extern "C" int dpe_attn_bwd(const AttnArgs& a, hipStream_t st) {
+  const int route = dpe_attn_route(a, nullptr);
+  if (route == AR_NONE) return -1;
+  const AttnLaunch l(a);
+  // dQ over the query heads; dK / dV over the K / V heads (GQA: each walking its group of query heads)
+  const dim3 gq(a.B * a.H * ((a.T + FQ - 1) / FQ)), gk(a.B * (a.Hkv ? a.Hkv : a.H) * ((a.T + BKW - 1) / BKW)), blk(256);
+  // dQ first: it also writes delta = rowsum(dO * O) (O is the dropped output under dropout), which the dK/dV kernel reads
+  if (route == AR_STAGED) {
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, blk, 0, st, a.qkv, a.out, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T, a.H, l.sl2,
+                       a.scale);
+    hipLaunchKernelGGL(attn_bwd_kernel, gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T, a.H, l.sl2, a.scale);
     return 0;
   }
-#ifdef DPE_ATTN_BWD_STAGED
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2, scale);
-  hipLaunchKernelGGL(attn_bwd_kernel, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale);
-  (void)dma;
-#else
-  if (dma) {
-    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, false>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, (const int*)nullptr, AttnDrop{}, 0);
-    hipLaunchKernelGGL((attn_bwd_dma_kernel<false, false>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       (const int*)nullptr, (const int*)nullptr, AttnDrop{}, 0);
-  } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H, sl2, scale);
-    hipLaunchKernelGGL(attn_bwd_kernel, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale);
-  }
-#endif
-  return 0;
-}
-
-// Dropout on P (thr in [1, 255]: drop rate thr / 256; rng = device int64[2] (seed, offset); stream = the call site).
-// LDS-DMA kernels only: a shape or switch that would take the register-staged kernels is an error, as for packed
-// documents.  doc_start / doc_end as above (null = plain causal).
-extern "C" int dpe_attn_fwd_drop(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale,
-                                 int causal, const int32_t* doc_start, const int32_t* doc_end, const int64_t* rng,
-                                 uint32_t stream, uint32_t thr, hipStream_t st) {
-  if (D != AD || T % AKV != 0 || !causal || !rng || thr < 1 || thr > 255) return -1;
-  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
-  if ((doc_start != nullptr) != (doc_end != nullptr)) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  const dim3 grid(B * H * ((T + FQ - 1) / FQ));
-  const AttnDrop dr{rng, stream, thr};
-  if (doc_start)
-    hipLaunchKernelGGL((attn_fwd_dma_kernel<true, true>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2, doc_start, dr, 0);
-  else
-    hipLaunchKernelGGL((attn_fwd_dma_kernel<false, true>), grid, dim3(256), 0, st, qkv, out, lse, B, T, H, sl2,
-                       (const int*)nullptr, dr, 0);
-  return 0;
-}
-
-extern "C" int dpe_attn_bwd_drop(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
-                                 float* delta, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal,
-                                 const int32_t* doc_start, const int32_t* doc_end, const int64_t* rng, uint32_t stream,
-                                 uint32_t thr, hipStream_t st) {
-  if (D != AD || T % AKV != 0 || !causal || !rng || thr < 1 || thr > 255) return -1;
-  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
-  if ((doc_start != nullptr) != (doc_end != nullptr)) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  const dim3 gq(B * H * ((T + FQ - 1) / FQ)), gk(B * H * ((T + BKW - 1) / BKW));
-  const AttnDrop dr{rng, stream, thr};
-  // dQ first: it also writes delta = rowsum(dO * O) (O is the dropped output), which the dK/dV kernel reads
-  if (doc_start) {
-    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<true, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, doc_start, dr, 0);
-    hipLaunchKernelGGL((attn_bwd_dma_kernel<true, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       doc_start, doc_end, dr, 0);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, H,
-                       sl2, scale, (const int*)nullptr, dr, 0);
-    hipLaunchKernelGGL((attn_bwd_dma_kernel<false, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2, scale,
-                       (const int*)nullptr, (const int*)nullptr, dr, 0);
-  }
-  return 0;
-}
-
-// Bidirectional attention over the first seq_len rows (1 <= seq_len <= T; the rows from seq_len on are padding: out and
-// dqkv get exact zeros there).  LDS-DMA kernels only, no doc_start, no dropout: a shape or switch that would take the
-// register-staged kernels is an error, as for packed documents.
-extern "C" int dpe_attn_fwd_bidir(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale,
-                                  int seq_len, hipStream_t st) {
-  if (D != AD || T % AKV != 0 || seq_len < 1 || seq_len > T) return -1;
-  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL((attn_fwd_dma_kernel<false, false, true>), dim3(B * H * ((T + FQ - 1) / FQ)), dim3(256), 0, st, qkv, out,
-                     lse, B, T, H, sl2, (const int*)nullptr, AttnDrop{}, seq_len);
-  return 0;
-}
-
-extern "C" int dpe_attn_bwd_bidir(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
-                                  float* delta, uint16_t* dqkv, int B, int T, int H, int D, float scale, int seq_len,
-                                  hipStream_t st) {
-  if (D != AD || T % AKV != 0 || seq_len < 1 || seq_len > T) return -1;
-  if (g_attn_staged || (int64_t)T * 3 * H * AD * 2 >= (1LL << 31)) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  const dim3 gq(B * H * ((T + FQ - 1) / FQ)), gk(B * H * ((T + BKW - 1) / BKW));
-  // dQ first: it also writes delta = rowsum(dO * O), which the dK/dV kernel reads
-  hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<false, false, true>), gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T,
-                     H, sl2, scale, (const int*)nullptr, AttnDrop{}, seq_len);
-  hipLaunchKernelGGL((attn_bwd_dma_kernel<false, false, true>), gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, H, sl2,
-                     scale, (const int*)nullptr, (const int*)nullptr, AttnDrop{}, seq_len);
-  return 0;
-}
-
-// Grouped-query attention (causal; doc_start / doc_end as above): qkv [B, T, Hq + 2 Hkv, 64], out [B, T, Hq, 64], lse and
-// delta [B, Hq, T], Hq % Hkv == 0 (Hkv == Hq is today's layout).  LDS-DMA kernels only, no dropout: a shape or switch
-// that would take the register-staged kernels is an error, as for packed documents.
-static bool gqa_ok(int T, int Hq, int Hkv, int D, const int32_t* doc_start, const int32_t* doc_end) {
-  if (D != AD || T < AKV || T % AKV != 0 || Hkv < 1 || Hq < Hkv || Hq % Hkv != 0) return false;
-  if ((doc_start != nullptr) != (doc_end != nullptr)) return false;
-  // one sequence's qkv rows must fit the DMA kernels' 32-bit buffer range
-  return !g_attn_staged && (int64_t)T * (Hq + 2 * Hkv) * AD * 2 < (1LL << 31);
-}
-
-extern "C" int dpe_attn_fwd_gqa(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int Hq, int Hkv, int D,
-                                float scale, const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
-  if (!gqa_ok(T, Hq, Hkv, D, doc_start, doc_end)) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  const dim3 grid(B * Hq * ((T + FQ - 1) / FQ));
-  if (doc_start)
-    hipLaunchKernelGGL(attn_fwd_gqa_kernel<true>, grid, dim3(256), 0, st, qkv, out, lse, B, T, Hq, Hkv, sl2, doc_start);
-  else
-    hipLaunchKernelGGL(attn_fwd_gqa_kernel<false>, grid, dim3(256), 0, st, qkv, out, lse, B, T, Hq, Hkv, sl2, (const int*)nullptr);
-  return 0;
-}
-
-extern "C" int dpe_attn_bwd_gqa(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
-                                float* delta, uint16_t* dqkv, int B, int T, int Hq, int Hkv, int D, float scale,
-                                const int32_t* doc_start, const int32_t* doc_end, hipStream_t st) {
-  if (!gqa_ok(T, Hq, Hkv, D, doc_start, doc_end)) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  // dQ over the query heads first (it also writes delta); dK / dV over the KV heads, each walking its group
-  const dim3 gq(B * Hq * ((T + FQ - 1) / FQ)), gk(B * Hkv * ((T + BKW - 1) / BKW));
-  if (doc_start) {
-    hipLaunchKernelGGL(attn_bwd_dq_gqa_kernel<true>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2,
-                       scale, doc_start);
-    hipLaunchKernelGGL(attn_bwd_gqa_kernel<true>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2, scale,
-                       doc_start, doc_end);
-  } else {
-    hipLaunchKernelGGL(attn_bwd_dq_gqa_kernel<false>, gq, dim3(256), 0, st, qkv, out, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2,
-                       scale, (const int*)nullptr);
-    hipLaunchKernelGGL(attn_bwd_gqa_kernel<false>, gk, dim3(256), 0, st, qkv, dout, lse, delta, dqkv, B, T, Hq, Hkv, sl2, scale,
-                       (const int*)nullptr, (const int*)nullptr);
-  }
+  with_mode(a, [&](auto P, auto Dr, auto Bi) {
+    constexpr bool PACKED = decltype(P)::value, DROP = decltype(Dr)::value, BIDIR = decltype(Bi)::value;
+    if (route == AR_GQA) {
+      hipLaunchKernelGGL(attn_bwd_dq_gqa_kernel<PACKED>, gq, blk, 0, st, a.qkv, a.out, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T,
+                         a.H, a.Hkv, l.sl2, a.scale, a.doc_start);
+      hipLaunchKernelGGL(attn_bwd_gqa_kernel<PACKED>, gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T, a.H,
+                         a.Hkv, l.sl2, a.scale, a.doc_start, a.doc_end);
+    } else {
+      hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<PACKED, DROP, BIDIR>), gq, blk, 0, st, a.qkv, a.out, a.dout, a.lse, a.delta,
+                         a.dqkv, a.B, a.T, a.H, l.sl2, a.scale, a.doc_start, l.dr, l.L);
+      hipLaunchKernelGGL((attn_bwd_dma_kernel<PACKED, DROP, BIDIR>), gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta, a.dqkv, a.B,
+                         a.T, a.H, l.sl2, a.scale, a.doc_start, a.doc_end, l.dr, l.L);
+    }
+  });
   return 0;
 }

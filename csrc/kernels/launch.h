@@ -1,6 +1,6 @@
 // The one declaration of every host launcher that takes plain pointers, included by the .hip file that defines it
 // and by every caller: a prototype that disagrees with its definition is a compile error ("conflicting types"), not
-// a call that links and passes garbage.  Launchers with argument structs: igemm.h, hgemm.h, pwconv.h.
+// a call that links and passes garbage.  Launchers with argument structs: igemm.h, hgemm.h, pwconv.h, attn.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -170,34 +170,8 @@ int dpe_layernorm_bwd(const uint16_t* dy, const void* x, int x_bf16, const float
                       float* part, int64_t rows, int D, hipStream_t st);
 int dpe_layernorm_bwd_finalize_group(const float* const* parts, const int64_t* rows, const int* Ds, float* const* dws,
                                      float* const* dbs, int n, hipStream_t st);
-// ---- attn.hip
-// doc_start / doc_end: the packed-document mask (int32 [B, T], both or neither; null = plain causal)
-int dpe_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int causal,
-                 const int32_t* doc_start, const int32_t* doc_end, hipStream_t st);
-int dpe_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                 float* dq_acc, uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, const int32_t* doc_start,
-                 const int32_t* doc_end, hipStream_t st);
+// ---- attn.hip (the launchers: attn.h)
 int dpe_set_attn_staged(int on);
-// dropout on P (LDS-DMA kernels only): rng = device int64[2] (seed, offset), stream = call site, drop rate thr / 256
-int dpe_attn_fwd_drop(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int causal,
-                      const int32_t* doc_start, const int32_t* doc_end, const int64_t* rng, uint32_t stream, uint32_t thr,
-                      hipStream_t st);
-int dpe_attn_bwd_drop(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                      uint16_t* dqkv, int B, int T, int H, int D, float scale, int causal, const int32_t* doc_start,
-                      const int32_t* doc_end, const int64_t* rng, uint32_t stream, uint32_t thr, hipStream_t st);
-// bidirectional attention over the first seq_len rows (1 <= seq_len <= T; out / dqkv rows from seq_len on are zeros);
-// LDS-DMA kernels only, no doc_start, no dropout
-int dpe_attn_fwd_bidir(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int D, float scale, int seq_len,
-                       hipStream_t st);
-int dpe_attn_bwd_bidir(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                       uint16_t* dqkv, int B, int T, int H, int D, float scale, int seq_len, hipStream_t st);
-// grouped-query attention (causal; LDS-DMA kernels only, no dropout): qkv [B, T, Hq + 2 Hkv, 64], Hq % Hkv == 0;
-// out [B, T, Hq, 64], lse / delta [B, Hq, T]; doc_start / doc_end as above
-int dpe_attn_fwd_gqa(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int Hq, int Hkv, int D, float scale,
-                     const int32_t* doc_start, const int32_t* doc_end, hipStream_t st);
-int dpe_attn_bwd_gqa(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
-                     uint16_t* dqkv, int B, int T, int Hq, int Hkv, int D, float scale, const int32_t* doc_start,
-                     const int32_t* doc_end, hipStream_t st);
 // ---- decode.hip
 // one query per (b, h) against the head-major cache kc / vc [B, H, Tmax, 64]; qkv_step [B, 3, H, 64]; len int32 [B]
 // (clamped into [0, Tmax - 1]); S key splits (ws: dpe_attn_decode_ws_floats fp32, unused for S = 1); out [B, H * 64]

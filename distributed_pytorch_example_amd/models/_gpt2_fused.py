@@ -206,20 +206,21 @@ class BlockFn(Function):
         qkv = C.linear_fwd(h1, shadow(blk.c_attn.weight), opt(blk.c_attn.bias), 0, False, None, None)
         qkv5 = qkv.view(B, T, 3, H, hd)
         bidir = getattr(blk, "seq_len", None)  # Block's attention mode: None causal, else the bidirectional key bound
+        # the attention mode: keyword arguments of C.attn_fwd, kept for C.attn_bwd
         if bidir is not None:
             if drop is not None or doc is not None:
                 raise ValueError("the bidirectional block takes neither dropout nor packed documents")
-            a, lse = C.attn_fwd(qkv5, H, scale, False, seq_len=bidir)
-        elif drop is not None:
-            # dropout (p, rng snapshot, first stream): on P inside the attention kernels; the projections write
-            # bf16 and dropout_add forms the fp32 x + dropout(proj) (no fp32-residual GEMM epilogue here)
-            dp, rng, ds0 = drop
-            a, lse = C.attn_fwd(qkv5, H, scale, True, doc_start=None if doc is None else doc[0],
-                                doc_end=None if doc is None else doc[1], dropout_p=dp, rng=rng, stream=ds0)
-        elif doc is None:
-            a, lse = C.attn_fwd(qkv5, H, scale, True)
-        else:  # packed documents: (doc_start, doc_end, pos) of Fx.doc_bounds
-            a, lse = C.attn_fwd(qkv5, H, scale, True, doc_start=doc[0], doc_end=doc[1])
+            mode = dict(causal=False, seq_len=bidir)
+        else:
+            mode = {}
+            if doc is not None:  # packed documents: (doc_start, doc_end, pos) of Fx.doc_bounds
+                mode.update(doc_start=doc[0], doc_end=doc[1])
+            if drop is not None:
+                # dropout (p, rng snapshot, first stream): on P inside the attention kernels; the projections write
+                # bf16 and dropout_add forms the fp32 x + dropout(proj) (no fp32-residual GEMM epilogue here)
+                dp, rng, ds0 = drop
+                mode.update(dropout_p=dp, rng=rng, stream=ds0)
+        a, lse = C.attn_fwd(qkv5, H, scale, **mode)
         a = a.view(B, T, D)
         if drop is not None:
             pa = C.linear_fwd(a, shadow(blk.attn_proj.weight), opt(blk.attn_proj.bias), 0, False, None, None)
@@ -236,7 +237,7 @@ class BlockFn(Function):
         else:
             y = C.linear_fwd(u, shadow(blk.mlp_proj.weight), opt(blk.mlp_proj.bias), 0, True, x2, None)
         ctx.save_for_backward(x, h1, m1, r1, qkv5, a, lse, x2, h2, m2, r2, v, u)
-        ctx.blk, ctx.scale, ctx.doc, ctx.drop, ctx.bidir = blk, scale, doc, drop, bidir
+        ctx.blk, ctx.scale, ctx.drop, ctx.attn_mode = blk, scale, drop, mode
         for p in params:
             note_use(p)
         return y
@@ -319,16 +320,7 @@ class BlockFn(Function):
             g2b = C.dropout_cast(g2, drop[0], drop[1], drop[2] + 1)
         da = linear_bwd(blk.attn_proj, g2b, a)
         a4 = a.view(qkv5.shape[0], qkv5.shape[1], qkv5.shape[3], qkv5.shape[4])
-        if ctx.bidir is not None:
-            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, False, seq_len=ctx.bidir)
-        elif drop is not None:
-            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True,
-                              doc_start=None if ctx.doc is None else ctx.doc[0],
-                              doc_end=None if ctx.doc is None else ctx.doc[1], dropout_p=drop[0], rng=drop[1], stream=drop[2])
-        elif ctx.doc is None:
-            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True)
-        else:
-            dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, True, doc_start=ctx.doc[0], doc_end=ctx.doc[1])
+        dqkv = C.attn_bwd(qkv5, a4, da, lse, blk.n_head, ctx.scale, **ctx.attn_mode)
         dqkv = dqkv.view(a.shape[0], a.shape[1], -1)
         dh1 = linear_bwd(blk.c_attn, dqkv, h1)
         g1, g1b = ln_bwd(blk.ln_1, dh1, x, m1, r1, g2)

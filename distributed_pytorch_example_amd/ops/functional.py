@@ -953,53 +953,23 @@ def check_doc_start(doc_start) -> None:
 
 
 class _AttnFn(Function):
+    """The flash-attention kernels in any mode.  ``mode``: the keyword arguments of C.attn_fwd that select it (doc_start /
+    doc_end; dropout_p / rng / stream; causal / seq_len; n_kv_head), handed to C.attn_bwd unchanged -- under dropout rng
+    is the forward's snapshot.  qkv: [B, T, 3, H, 64], or [B, T, H + 2 n_kv_head, 64]."""
+
     @staticmethod
-    def forward(ctx, qkv, H: int, scale: float, doc_start=None, doc_end=None, dropout_p: float = 0.0, rng=None,
-                stream: int = 0):
-        ctx.drop = None
-        if dropout_p > 0.0:  # dropout on P inside the kernels; rng is the forward's snapshot, kept for backward
-            ctx.drop = dict(dropout_p=dropout_p, rng=rng, stream=stream)
-            out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True, doc_start=doc_start, doc_end=doc_end, **ctx.drop)
-        elif doc_start is None:
-            out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True)
-        else:
-            out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True, doc_start=doc_start, doc_end=doc_end)
+    def forward(ctx, qkv, H: int, scale: float, mode: dict):
+        qkv = qkv.contiguous()
+        out, lse = ext().attn_fwd(qkv, H, scale, **mode)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.H, ctx.scale, ctx.doc = H, scale, (doc_start, doc_end)
+        ctx.args = H, scale, mode
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        ds, de = ctx.doc
-        if ctx.drop is not None:
-            dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True,
-                                  doc_start=ds, doc_end=de, **ctx.drop)
-        elif ds is None:
-            dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True)
-        else:
-            dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, True,
-                                  doc_start=ds, doc_end=de)
-        return dqkv, None, None, None, None, None, None, None
-
-
-class _GqaAttnFn(Function):
-    """Grouped-query causal attention on the GQA kernels: qkv [B, T, Hq + 2 Hkv, 64], optional packed documents."""
-
-    @staticmethod
-    def forward(ctx, qkv, H: int, Hkv: int, scale: float, doc_start=None, doc_end=None):
-        out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, True, doc_start=doc_start, doc_end=doc_end, n_kv_head=Hkv)
-        ctx.save_for_backward(qkv, out, lse)
-        ctx.args = H, Hkv, scale, doc_start, doc_end
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        H, Hkv, scale, ds, de = ctx.args
-        dqkv = ext().attn_bwd(qkv.contiguous(), out, dout.contiguous().to(torch.bfloat16), lse, H, scale, True,
-                              doc_start=ds, doc_end=de, n_kv_head=Hkv)
-        return dqkv, None, None, None, None, None
+        H, scale, mode = ctx.args
+        return ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, H, scale, **mode), None, None, None
 
 
 def _gqa_attention(qkv, n_head: int, n_kv_head: int, doc_bounds):
@@ -1011,8 +981,8 @@ def _gqa_attention(qkv, n_head: int, n_kv_head: int, doc_bounds):
     scale = 1.0 / math.sqrt(D)
     ds, de = (doc_bounds[0], doc_bounds[1]) if doc_bounds is not None else (None, None)
     if qkv.is_cuda and attn_kernel_ok(T, D):
-        out = _GqaAttnFn.apply(qkv.reshape(B, T, n_head + 2 * n_kv_head, D), n_head, n_kv_head, scale, ds, de)
-        return out.reshape(B, T, n_head * D)
+        mode = dict(doc_start=ds, doc_end=de, n_kv_head=n_kv_head)
+        return _AttnFn.apply(qkv.reshape(B, T, n_head + 2 * n_kv_head, D), n_head, scale, mode).reshape(B, T, n_head * D)
     # off the GPU and for other shapes: K / V expanded to one head per query head, then the explicit softmax
     q, k, v = qkv.reshape(B, T, n_head + 2 * n_kv_head, D).split([n_head, n_kv_head, n_kv_head], dim=2)
     g = n_head // n_kv_head
@@ -1060,51 +1030,24 @@ def causal_attention(qkv, n_head: int, doc_bounds=None, dropout_p: float = 0.0, 
     B, T, three_hd = qkv.shape
     D = three_hd // (3 * n_head)
     scale = 1.0 / math.sqrt(D)
-    if dropout_p != 0.0:
-        if not 0.0 < dropout_p < 1.0:
-            raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
-        ds, de = (doc_bounds[0], doc_bounds[1]) if doc_bounds is not None else (None, None)
-        if not qkv.is_cuda or not attn_kernel_ok(T, D):
-            return _causal_attention_torch(qkv.reshape(B, T, 3, n_head, D), scale, ds, dropout_p).reshape(B, T, n_head * D)
+    if dropout_p != 0.0 and not 0.0 < dropout_p < 1.0:
+        raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
+    ds, de = (doc_bounds[0], doc_bounds[1]) if doc_bounds is not None else (None, None)
+    if not qkv.is_cuda and ds is None and dropout_p == 0.0:  # the plain causal call off the GPU, whatever its shape
+        q, k, v = qkv.float().view(B, T, 3, n_head, D).permute(2, 0, 3, 1, 4)
+        o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        return o.transpose(1, 2).reshape(B, T, n_head * D)
+    qkv5 = qkv.reshape(B, T, 3, n_head, D)
+    if not qkv.is_cuda or not attn_kernel_ok(T, D):
+        return _causal_attention_torch(qkv5, scale, ds, dropout_p).reshape(B, T, n_head * D)
+    mode = dict(doc_start=ds, doc_end=de)
+    if dropout_p != 0.0:  # dropout on P inside the kernels; rng is the forward's snapshot, kept for backward
         if rng is None:
             st = dropout_state(qkv.device)
             rng = st.snapshot()
             st.advance(B * n_head * (T // 4) ** 2)
-        out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, ds, de, dropout_p, rng, stream)
-        return out.reshape(B, T, n_head * D)
-    if doc_bounds is not None:
-        ds, de = doc_bounds[0], doc_bounds[1]
-        if not qkv.is_cuda or not attn_kernel_ok(T, D):
-            return _causal_attention_torch(qkv.reshape(B, T, 3, n_head, D), scale, ds).reshape(B, T, n_head * D)
-        out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, ds, de)
-        return out.reshape(B, T, n_head * D)
-    if not qkv.is_cuda:
-        q, k, v = qkv.float().view(B, T, 3, n_head, D).permute(2, 0, 3, 1, 4)
-        o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-        return o.transpose(1, 2).reshape(B, T, n_head * D)
-    if not attn_kernel_ok(T, D):
-        return _causal_attention_torch(qkv.reshape(B, T, 3, n_head, D), scale).reshape(B, T, n_head * D)
-    out = _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, None, None)
-    return out.reshape(B, T, n_head * D)
-
-
-class _BidirAttnFn(Function):
-    """Bidirectional attention over the first ``seq_len`` rows on the LDS-DMA kernels (causal=False); the rows from
-    ``seq_len`` on are padding: zeros in the output and in all three parts of the gradient."""
-
-    @staticmethod
-    def forward(ctx, qkv, H: int, scale: float, seq_len: int):
-        out, lse = ext().attn_fwd(qkv.contiguous(), H, scale, False, seq_len=seq_len)
-        ctx.save_for_backward(qkv, out, lse)
-        ctx.H, ctx.scale, ctx.seq_len = H, scale, seq_len
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        dqkv = ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, ctx.H, ctx.scale, False,
-                              seq_len=ctx.seq_len)
-        return dqkv, None, None, None
+        mode.update(dropout_p=dropout_p, rng=rng, stream=stream)
+    return _AttnFn.apply(qkv5, n_head, scale, mode).reshape(B, T, n_head * D)
 
 
 def _attention_torch(qkv5, scale: float, seq_len: int):
@@ -1130,7 +1073,9 @@ def attention(qkv, n_head: int, seq_len: Optional[int] = None):
     scale = 1.0 / math.sqrt(D)
     if not qkv.is_cuda or not attn_kernel_ok(T, D):
         return _attention_torch(qkv.reshape(B, T, 3, n_head, D), scale, L).reshape(B, T, n_head * D)
-    return _BidirAttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, L).reshape(B, T, n_head * D)
+    # causal=False: the rows from seq_len on are padding, zeros in the output and in all three parts of the gradient
+    mode = dict(causal=False, seq_len=L)
+    return _AttnFn.apply(qkv.reshape(B, T, 3, n_head, D), n_head, scale, mode).reshape(B, T, n_head * D)
 
 
 def patchify(x: torch.Tensor, patch: int) -> torch.Tensor:

@@ -244,6 +244,28 @@ def test_set_attn_staged_returns_previous(C):
         C.set_attn_staged(prev)
 
 
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "bidir"])
+@pytest.mark.parametrize("bad", ["qkv_f32", "qkv_strided", "lse_short", "out_half"])
+def test_attn_bwd_refuses_bad_tensors(C, bad, causal):
+    """The kernels index qkv, out, dout and lse by B, T, H: attn_bwd refuses a tensor of another dtype, stride or size
+    in every mode (no n_kv_head here), before any launch."""
+    qkv = torch.zeros(1, 64, 3, 1, 64, dtype=BF, device=dev)
+    out, dout = torch.zeros(1, 64, 1, 64, dtype=BF, device=dev), torch.zeros(1, 64, 1, 64, dtype=BF, device=dev)
+    lse = torch.zeros(1, 1, 64, device=dev)
+    if bad == "qkv_f32":
+        qkv = qkv.float()
+    elif bad == "qkv_strided":
+        qkv = torch.zeros(1, 64, 3, 1, 128, dtype=BF, device=dev)[..., ::2]
+        assert qkv.shape == (1, 64, 3, 1, 64) and not qkv.is_contiguous()
+    elif bad == "lse_short":
+        lse = lse[..., :32].contiguous()
+    else:
+        out = out[:, :32].contiguous()
+    with pytest.raises(RuntimeError):
+        C.attn_bwd(qkv, out, dout, lse, 1, SCALE, causal)
+    torch.cuda.synchronize()
+
+
 # ------------------------------------------------- 3. shapes outside the kernels
 @pytest.mark.parametrize("T,D", [(100, 64), (65, 64), (128, 32)])
 def test_causal_attention_unsupported_shapes(C, T, D):
