@@ -665,6 +665,103 @@ Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const 
   return dqkv;
 }
 
+// ------------------------------------------------- RoPE, RMSNorm, SwiGLU (llama.hip)
+// src bf16 [B, T, W, 64]: heads [0, n_rot) rotated by the table row pos[b, t] (int32 [B, T]; default t, which needs
+// T <= P) of cos / sin fp32 [P, 32]; out = src rotates in place, out = None returns a new tensor with the other heads
+// copied.  inverse: the transposed rotation (the backward).
+Tensor rope(const Tensor& src, const Tensor& cos, const Tensor& sin, const c10::optional<Tensor>& pos, int64_t n_rot,
+            bool inverse, const c10::optional<Tensor>& out_) {
+  CHECK_GPU(src);
+  TORCH_CHECK(src.dim() == 4, "rope: src must be [B, T, W, 64]");
+  const int64_t B = src.size(0), T = src.size(1), W = src.size(2);
+  TORCH_CHECK(src.size(3) == 64, "rope: src's head dim must be 64, got ", src.size(3));
+  TORCH_CHECK(B >= 1 && T >= 1 && W >= 1 && B * T < (1ll << 31), "rope: src must have 1 <= B * T < 2^31 tokens and a head");
+  TORCH_CHECK(n_rot >= 0 && n_rot <= W, "rope: n_rot = ", n_rot, " must be in [0, W = ", W, "]");
+  checked("rope", "src", src, src, at::kBFloat16, B * T * W * 64);
+  TORCH_CHECK(cos.dim() == 2 && cos.size(0) >= 1 && cos.size(1) == 32, "rope: cos must be [P, 32]");
+  const int64_t P = cos.size(0);
+  const float* cp = (const float*)checked("rope", "cos", cos, src, at::kFloat, P * 32);
+  const float* sp = (const float*)checked("rope", "sin", sin, src, at::kFloat, P * 32);
+  TORCH_CHECK(P < (1ll << 26), "rope: cos has too many rows");
+  TORCH_CHECK(has(pos) || T <= P, "rope: pos = None needs T <= P (T = ", T, ", P = ", P, ")");
+  const int32_t* pp = has(pos) ? (const int32_t*)checked("rope", "pos", *pos, src, at::kInt, B * T) : nullptr;
+  Tensor out = has(out_) ? *out_ : at::empty_like(src);
+  checked("rope", "out", out, src, at::kBFloat16, src.numel());
+  CHECK_RC(dpe_rope(bp(src), bpm(out), cp, sp, pp, (int)B, (int)T, (int)W, (int)n_rot, (int)P, inverse ? 1 : 0, cur_stream()),
+           "rope");
+  return out;
+}
+
+// x [rows, D] fp32 or bf16 -> (y bf16, rstd fp32 [rows]): y = x rstd w, rstd = rsqrt(mean(x^2) + eps), in fp32 with one
+// rounding (not HF's form, which rounds x rstd to the input dtype before the gain).  D % 8 == 0, 8 <= D <= 8192.
+int64_t rms_dims(const char* fn, const Tensor& x, const Tensor& w, bool* xb) {
+  CHECK_GPU(x);
+  *xb = x.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(*xb || x.scalar_type() == at::kFloat, fn, ": x must be float32 or bfloat16");
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, fn, ": x must be [..., D] and not empty");
+  const int64_t D = x.size(-1);
+  TORCH_CHECK(D % 8 == 0 && D >= 8 && D <= 8192, fn, ": D = ", D, " must be a multiple of 8 in [8, 8192]");
+  checked(fn, "x", x, x, x.scalar_type(), x.numel());
+  checked(fn, "w", w, x, at::kFloat, D);
+  return D;
+}
+
+std::vector<Tensor> rmsnorm_fwd(const Tensor& x, const Tensor& w, double eps) {
+  bool xb;
+  const int64_t D = rms_dims("rmsnorm_fwd", x, w, &xb), rows = x.numel() / D;
+  Tensor y = at::empty(x.sizes(), x.options().dtype(at::kBFloat16));
+  Tensor rstd = at::empty({rows}, x.options().dtype(at::kFloat));
+  CHECK_RC(dpe_rmsnorm_fwd(x.data_ptr(), xb, fp(w), bpm(y), fp(rstd), rows, (int)D, (float)eps, cur_stream()), "rmsnorm_fwd");
+  return {y, rstd};
+}
+
+// -> dx in x's dtype; dw fp32 [D] is accumulated into
+Tensor rmsnorm_bwd(const Tensor& dy, const Tensor& x, const Tensor& w, const Tensor& rstd, Tensor& dw) {
+  bool xb;
+  const int64_t D = rms_dims("rmsnorm_bwd", x, w, &xb), rows = x.numel() / D;
+  checked("rmsnorm_bwd", "dy", dy, x, at::kBFloat16, x.numel());
+  checked("rmsnorm_bwd", "rstd", rstd, x, at::kFloat, rows);
+  checked("rmsnorm_bwd", "dw", dw, x, at::kFloat, D);
+  Tensor dx = at::empty_like(x);
+  Tensor part = at::empty({dpe_rmsnorm_bwd_scratch(rows, (int)D)}, x.options().dtype(at::kFloat));
+  CHECK_RC(dpe_rmsnorm_bwd(bp(dy), x.data_ptr(), xb, fp(w), fp(rstd), dx.data_ptr(), fp(dw), fp(part), rows, (int)D,
+                           cur_stream()), "rmsnorm_bwd");
+  return dx;
+}
+
+// gu bf16 [..., 2 F] = [gate | up] -> u = silu(gate) up, bf16 [..., F]; F % 8 == 0
+int64_t swiglu_dims(const char* fn, const Tensor& gu, int64_t* M) {
+  CHECK_GPU(gu);
+  TORCH_CHECK(gu.dim() >= 1 && gu.numel() > 0 && gu.size(-1) % 16 == 0, fn, ": gu must be [..., 2 F] with F % 8 == 0");
+  const int64_t F = gu.size(-1) / 2;
+  *M = gu.numel() / (2 * F);
+  TORCH_CHECK(*M * (F / 8) < (1ll << 31) && F < (1ll << 31), fn, ": gu is too large (M * F / 8 must be below 2^31)");
+  checked(fn, "gu", gu, gu, at::kBFloat16, gu.numel());
+  return F;
+}
+
+Tensor swiglu_fwd(const Tensor& gu, const c10::optional<Tensor>& out_) {
+  int64_t M;
+  const int64_t F = swiglu_dims("swiglu_fwd", gu, &M);
+  auto sz = gu.sizes().vec();
+  sz.back() = F;
+  Tensor u = has(out_) ? *out_ : at::empty(sz, gu.options());
+  checked("swiglu_fwd", "out", u, gu, at::kBFloat16, M * F);
+  CHECK_RC(dpe_swiglu_fwd(bp(gu), bpm(u), M, (int)F, cur_stream()), "swiglu_fwd");
+  return u;
+}
+
+// -> dgu bf16 of gu's shape: [d gate | d up], sigma(gate) recomputed from gu
+Tensor swiglu_bwd(const Tensor& du, const Tensor& gu, const c10::optional<Tensor>& out_) {
+  int64_t M;
+  const int64_t F = swiglu_dims("swiglu_bwd", gu, &M);
+  checked("swiglu_bwd", "du", du, gu, at::kBFloat16, M * F);
+  Tensor dgu = has(out_) ? *out_ : at::empty_like(gu);
+  checked("swiglu_bwd", "out", dgu, gu, at::kBFloat16, gu.numel());
+  CHECK_RC(dpe_swiglu_bwd(bp(du), bp(gu), bpm(dgu), M, (int)F, cur_stream()), "swiglu_bwd");
+  return dgu;
+}
+
 }  // namespace
 
 void register_ops(pybind11::module& m) {
@@ -720,6 +817,14 @@ void register_ops(pybind11::module& m) {
   m.def("layernorm_fwd", &layernorm_fwd, py::arg("x"), py::arg("w"), py::arg("b") = py::none(), py::arg("eps") = 1e-5);
   m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("mean"), py::arg("rstd"),
         py::arg("dw"), py::arg("db") = py::none(), py::arg("dx_out") = py::none());
+  m.def("rope", &rope, py::arg("src"), py::arg("cos"), py::arg("sin"), py::arg("pos") = py::none(), py::arg("n_rot"),
+        py::arg("inverse") = false, py::arg("out") = py::none(),
+        "rotate-half RoPE on the first n_rot heads of bf16 [B, T, W, 64]; out = src: in place; inverse: the backward");
+  m.def("rmsnorm_fwd", &rmsnorm_fwd, py::arg("x"), py::arg("w"), py::arg("eps") = 1e-5, "-> (y bf16, rstd fp32 [rows])");
+  m.def("rmsnorm_bwd", &rmsnorm_bwd, py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("rstd"), py::arg("dw"),
+        "-> dx in x's dtype; dw (fp32 [D]) is accumulated into");
+  m.def("swiglu_fwd", &swiglu_fwd, py::arg("gu"), py::arg("out") = py::none(), "gu [.., 2F] = [gate | up] -> silu(gate) up");
+  m.def("swiglu_bwd", &swiglu_bwd, py::arg("du"), py::arg("gu"), py::arg("out") = py::none(), "-> dgu = [d gate | d up]");
   m.def("cu_hog", [](int64_t nblocks, int64_t threads, int64_t lds_bytes, double us, int64_t vgprs,
                      const c10::optional<Tensor>& stop, bool sleepy, int64_t mode) {
           static Tensor sink = at::empty({1024}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA));

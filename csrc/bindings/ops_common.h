@@ -36,6 +36,16 @@ inline float* fp(const Tensor& t) { return (float*)t.data_ptr(); }
 inline const float* fpo(const c10::optional<Tensor>& t) { return has(t) ? (const float*)t->data_ptr() : nullptr; }
 inline float* fpom(const c10::optional<Tensor>& t) { return has(t) ? (float*)t->data_ptr() : nullptr; }
 
+// All four checks of one tensor argument -- on `like`'s GPU, of dtype `ty`, contiguous, n elements -- with a message
+// that names the op and the argument; returns its data pointer.
+inline void* checked(const char* fn, const char* name, const Tensor& t, const Tensor& like, at::ScalarType ty, int64_t n) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), fn, ": ", name, " must be a GPU tensor on ", like.device());
+  TORCH_CHECK(t.scalar_type() == ty, fn, ": ", name, " must be ", c10::toString(ty));
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", name, " must be contiguous");
+  TORCH_CHECK(t.numel() == n, fn, ": ", name, " must have ", n, " elements, has ", t.numel());
+  return t.data_ptr();
+}
+
 // An on/off environment switch.  Default on: only a value starting with '0' turns it off; default off: only '1' on.
 inline bool env_on(const char* name, bool dflt) {
   const char* e = getenv(name);

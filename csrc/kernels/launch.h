@@ -170,6 +170,22 @@ int dpe_layernorm_bwd(const uint16_t* dy, const void* x, int x_bf16, const float
                       float* part, int64_t rows, int D, hipStream_t st);
 int dpe_layernorm_bwd_finalize_group(const float* const* parts, const int64_t* rows, const int* Ds, float* const* dws,
                                      float* const* dbs, int n, hipStream_t st);
+// ---- llama.hip
+// src / dst bf16 [B, T, W, 64], the first n_rot heads of every token rotated (rotate-half) by row pos[b, t] (null: t,
+// T <= P) of cos / sin fp32 [P, 32], the row clamped into [0, P - 1]; inverse: the transposed rotation.  dst == src:
+// in place; else the other W - n_rot heads are copied through.
+int dpe_rope(const uint16_t* src, uint16_t* dst, const float* cos, const float* sin, const int32_t* pos, int B, int T, int W,
+             int n_rot, int P, int inverse, hipStream_t st);
+// D % 8 == 0, 8 <= D <= 8192; x fp32 or bf16, y bf16, rstd fp32 [rows]; dx in x's dtype, dw [D] accumulated into
+int dpe_rmsnorm_fwd(const void* x, int x_bf16, const float* w, uint16_t* y, float* rstd, int64_t rows, int D, float eps,
+                    hipStream_t st);
+int dpe_rmsnorm_bwd_nblocks(int64_t rows, int D);
+int64_t dpe_rmsnorm_bwd_scratch(int64_t rows, int D);
+int dpe_rmsnorm_bwd(const uint16_t* dy, const void* x, int x_bf16, const float* w, const float* rstd, void* dx, float* dw,
+                    float* part, int64_t rows, int D, hipStream_t st);
+// gu / dgu bf16 [M, 2 F] = [gate | up], u / du bf16 [M, F]; F % 8 == 0, M F / 8 < 2^31
+int dpe_swiglu_fwd(const uint16_t* gu, uint16_t* u, int64_t M, int F, hipStream_t st);
+int dpe_swiglu_bwd(const uint16_t* du, const uint16_t* gu, uint16_t* dgu, int64_t M, int F, hipStream_t st);
 // ---- attn.hip (the launchers: attn.h)
 int dpe_set_attn_staged(int on);
 // ---- decode.hip

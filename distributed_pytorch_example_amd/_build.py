@@ -38,9 +38,11 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # and dwconv7_rows_kernel goes from 173 / 181 VGPRs and no scratch to 256 VGPRs and 972 / 1000 B of scratch per lane
 # (bf16 / fp32 input); the kernels are specified scratch-free.  -fno-slp-vectorize alone gives the same ISA today; the
 # target feature holds whichever pass would form the packed ops.
+# llama.hip: the same feature; its 8-wide fp32 lanes are what the packer pairs, and nothing there is VALU-bound.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"attn.hip": ["-fno-slp-vectorize", "-fno-honor-nans"],
               "hgemm.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
-              "dwconv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "dwconv.hip": _NO_PK_F32, "llama.hip": _NO_PK_F32}
 
 
 def _torch_dirs():

@@ -850,6 +850,122 @@ def layer_norm(x, weight, bias=None, eps: float = 1e-5):
     return _LNFn.apply(x, weight, bias, eps)
 
 
+# ================================================= RMSNorm, RoPE, SwiGLU (Llama)
+class _RMSFn(Function):
+    @staticmethod
+    def forward(ctx, x, w, eps):
+        x = x.contiguous()
+        y, rstd = ext().rmsnorm_fwd(x, w.detach(), eps)
+        ctx.save_for_backward(x, rstd)
+        ctx.w = w
+        note_use(w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, rstd = ctx.saved_tensors
+        wbuf, wd = grad_sink(ctx.w)
+        dx = ext().rmsnorm_bwd(dy.contiguous().to(torch.bfloat16), x, ctx.w.detach(), rstd, wbuf)
+        grad_done(ctx.w, wd)
+        return dx, (None if wd else wbuf), None
+
+
+def rms_norm(x, weight, eps: float = 1e-5):
+    """RMSNorm over the last dim: ``x * rsqrt(mean(x^2) + eps) * weight``, carried in fp32 and rounded once.  GPU:
+    f32/bf16 in -> bf16 out, D % 8 == 0 and 8 <= D <= 8192.  This is not Hugging Face's form, which rounds
+    ``x * rstd`` to the input dtype before the gain is applied."""
+    if not x.is_cuda:
+        xf = x.float()
+        return xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * weight
+    return _RMSFn.apply(x, weight, eps)
+
+
+def rope_table(P: int, theta: float = 10000.0, device=None, head_dim: int = 64):
+    """(cos, sin), fp32 [P, 32] each, of the angles ``p * theta^(-2i/64)``: computed in fp64, rounded to fp32 once.
+    (``head_dim``: 64 is what the kernel takes; another even value gives [P, head_dim / 2] for the torch path.)"""
+    half = head_dim // 2
+    inv = torch.tensor(float(theta), dtype=torch.float64) ** (-torch.arange(half, dtype=torch.float64) / half)
+    ang = torch.arange(P, dtype=torch.float64)[:, None] * inv[None, :]
+    return ang.cos().float().to(device), ang.sin().float().to(device)
+
+
+def _rope_torch(x4, n_rot: int, table, pos):
+    """The rotation in fp32 torch ops on x4 [B, T, W, D], result in x4's dtype: any even head dim, any device."""
+    T, half = x4.shape[1], x4.shape[-1] // 2
+    cos, sin = table
+    rows = torch.arange(T, device=x4.device) if pos is None else pos.long().clamp(0, cos.shape[0] - 1)
+    c, s = cos[rows].unsqueeze(-2), sin[rows].unsqueeze(-2)  # [(B,) T, 1, half]
+    x1, x2 = x4[:, :, :n_rot, :half].float(), x4[:, :, :n_rot, half:].float()
+    rot = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1).to(x4.dtype)
+    return torch.cat([rot, x4[:, :, n_rot:]], dim=2)
+
+
+class _RopeFn(Function):
+    """qkv bf16 [B, T, W * 64], contiguous.  ``inplace``: qkv itself is rotated and returned (mark_dirty)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, pos, W: int, n_rot: int, inplace: bool):
+        B, T, w = qkv.shape
+        ctx.save_for_backward(cos, sin, pos)
+        ctx.W, ctx.n_rot = W, n_rot
+        x4 = qkv.view(B, T, W, 64)
+        if not inplace:
+            return ext().rope(x4, cos, sin, pos, n_rot, False, None).view(B, T, w)
+        ctx.mark_dirty(qkv)
+        ext().rope(x4, cos, sin, pos, n_rot, False, x4)
+        return qkv
+
+    @staticmethod
+    def backward(ctx, dy):
+        cos, sin, pos = ctx.saved_tensors
+        B, T, w = dy.shape
+        d4 = dy.contiguous().to(torch.bfloat16).view(B, T, ctx.W, 64)
+        return ext().rope(d4, cos, sin, pos, ctx.n_rot, True, None).view(B, T, w), None, None, None, None, None, None
+
+
+def rope(qkv, n_head: int, n_kv_head: int, table, pos=None, inplace: bool = False):
+    """Rotary position embedding (rotate-half, as HF Llama) on the query and key heads of qkv
+    [B, T, (n_head + 2 n_kv_head) * D]; the value heads pass through.  ``table``: rope_table's (cos, sin) [P, D / 2];
+    the row is ``pos[b, t]`` (int32 [B, T], doc_bounds()[2]) or t.  On the GPU with D = 64 the HIP kernel runs --
+    ``inplace`` rotates qkv itself (it must not be needed unrotated by an earlier op's backward); the backward is the
+    inverse rotation into a fresh tensor.  Elsewhere the same formula in torch ops."""
+    B, T, w = qkv.shape
+    W = n_head + 2 * n_kv_head
+    D = w // W
+    if w != W * D or D % 2 or table[0].shape != (table[0].shape[0], D // 2) or table[1].shape != table[0].shape:
+        raise ValueError(f"rope: qkv's last dim {w} and the [P, {table[0].shape[-1]}] table do not fit {W} heads")
+    if T > table[0].shape[0] and pos is None:
+        raise ValueError(f"rope: T = {T} exceeds the table's {table[0].shape[0]} rows")
+    if not qkv.is_cuda or D != 64:
+        return _rope_torch(qkv.reshape(B, T, W, D), n_head + n_kv_head, table, pos).reshape(B, T, w)
+    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():  # (a copy: nothing to rotate in place)
+        qkv, inplace = qkv.to(torch.bfloat16).contiguous(), False
+    pos = pos.to(torch.int32).contiguous() if pos is not None else None
+    return _RopeFn.apply(qkv, table[0], table[1], pos, W, n_head + n_kv_head, inplace)
+
+
+class _SwiGLUFn(Function):
+    @staticmethod
+    def forward(ctx, gu):
+        gu = gu.contiguous()
+        ctx.save_for_backward(gu)
+        return ext().swiglu_fwd(gu)
+
+    @staticmethod
+    def backward(ctx, du):
+        (gu,) = ctx.saved_tensors
+        return ext().swiglu_bwd(du.contiguous().to(torch.bfloat16), gu)
+
+
+def swiglu(gu):
+    """gu [..., 2 F] = [gate | up] (one GEMM against the row-concatenated [gate_proj; up_proj] weight) ->
+    ``silu(gate) * up`` [..., F].  GPU: bf16, F % 8 == 0; the backward recomputes sigmoid(gate) from gu."""
+    if not gu.is_cuda:
+        g, v = gu.chunk(2, dim=-1)
+        return F.silu(g) * v
+    return _SwiGLUFn.apply(gu if gu.dtype == torch.bfloat16 else gu.to(torch.bfloat16))
+
+
 # ================================================================ Embedding
 class _EmbFn(Function):
     @staticmethod

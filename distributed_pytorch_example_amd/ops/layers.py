@@ -140,6 +140,16 @@ class LayerNorm(nn.Module):
         return Fx.layer_norm(x, self.weight, self.bias, self.eps)
 
 
+class RMSNorm(nn.Module):
+    def __init__(self, dim: int, eps: float = 1e-5, device=None):
+        super().__init__()
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(dim, device=device))
+
+    def forward(self, x):
+        return Fx.rms_norm(x, self.weight, self.eps)
+
+
 class CrossEntropyLoss(nn.Module):
     """torch.nn.CrossEntropyLoss (mean, ``label_smoothing`` included) on the fused HIP kernel, plus an optional
     ``z_loss * mean(logsumexp^2)``."""

@@ -22,7 +22,7 @@ import torch
 from torch.distributed.elastic.multiprocessing.errors import record
 
 from .data import BatchMixer, SyntheticDataset, SyntheticTokens, create_data_loader
-from .models import get_model
+from .models import LLAMA_MODELS, get_model
 from .ops import functional as Fx
 from .optim import build_optimizer
 from .parallel import DDP
@@ -47,7 +47,7 @@ def build_parser() -> argparse.ArgumentParser:
     # ---- additive
     p.add_argument("--model", default="simplenet", choices=["simplenet", "resnet50", "resnet_tiny", "gpt2", "gpt2-tiny",
                                                                    "vit-tiny", "vit-s16", "vit-b16", "convnext-tiny",
-                                                                   "convnext-test"])
+                                                                   "convnext-test", "llama-tiny", "tinyllama-1.1b"])
     p.add_argument("--backend", default="auto", choices=["auto", "rccl", "nccl", "gloo"])
     p.add_argument("--dtype", default=None, choices=[None, "fp32", "bf16"],
                    help="compute dtype on the GPU (default: fp32 for simplenet as the reference, bf16 otherwise; "
@@ -110,7 +110,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="resnet, vit and convnext models: the square input size (default 224; vit-tiny and convnext-test 32)")
     p.add_argument("--seq-len", type=int, default=1024)
     p.add_argument("--doc-len-mean", type=float, default=None,
-                   help="gpt2 models: pack documents of this mean length (geometric) into every row; attention stays "
+                   help="gpt2 and llama models: pack documents of this mean length (geometric) into every row; attention stays "
                         "inside a document, positions restart, targets across a boundary are ignored")
     p.add_argument("--max-steps", type=int, default=None, help="stop each epoch after this many steps")
     p.add_argument("--async-checkpoint", action="store_true")
@@ -140,7 +140,7 @@ def _datasets(args, device):
         tr = SyntheticDataset(args.num_samples, shp, ncls, seed=args.seed)
         va = SyntheticDataset(max(1, args.num_samples // 10), shp, ncls, seed=None if args.seed is None else args.seed + 1)
         return tr, va, ncls
-    vocab = 50257 if args.model == "gpt2" else 512
+    vocab = {"gpt2": 50257, "tinyllama-1.1b": 32000}.get(args.model, 512)
     tr = SyntheticTokens(args.num_samples, args.seq_len, vocab, seed=args.seed, doc_len_mean=args.doc_len_mean)
     va = SyntheticTokens(max(1, args.num_samples // 10), args.seq_len, vocab, seed=None if args.seed is None else args.seed + 1,
                          doc_len_mean=args.doc_len_mean)
@@ -258,6 +258,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     vit = args.model.startswith("vit")
     convnext = args.model.startswith("convnext")
+    lm = args.model.startswith("gpt2") or args.model in LLAMA_MODELS  # token data, the model returns the fused loss
     if args.image_size is None:
         args.image_size = 32 if args.model in ("vit-tiny", "convnext-test") else 224
     if vit or convnext:
@@ -276,8 +277,8 @@ def main(argv=None):
         parser.error("--skip-nonfinite-steps needs --clip-grad-norm")
     if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
         parser.error("--clip-grad-norm must be > 0")
-    if args.doc_len_mean is not None and not args.model.startswith("gpt2"):
-        parser.error("--doc-len-mean needs a gpt2 model")
+    if args.doc_len_mean is not None and not lm:
+        parser.error("--doc-len-mean needs a gpt2 model or a llama model")
     if args.doc_len_mean is not None and not args.doc_len_mean >= 1:
         parser.error("--doc-len-mean must be >= 1")
     if args.trust_coefficient is not None and args.optimizer not in ("lars", "lamb"):
@@ -321,9 +322,9 @@ def main(argv=None):
             parser.error(f"{flag} needs --mixup-alpha or --cutmix-alpha")
         if v is not None and not 0.0 <= v <= 1.0:
             parser.error(f"{flag} must be in [0, 1]")
-    if args.model.startswith("gpt2") and (mixing or args.mix_prob is not None or args.mix_switch_prob is not None):
+    if lm and (mixing or args.mix_prob is not None or args.mix_switch_prob is not None):
         parser.error("--mixup-alpha / --cutmix-alpha / --mix-prob / --mix-switch-prob are for the image and feature "
-                     "models, not gpt2")
+                     "models, not gpt2 or llama")
     if args.cutmix_alpha > 0.0 and not args.model.startswith("resnet"):
         parser.error("--cutmix-alpha needs an image model (resnet50, resnet_tiny)")
     ensure_single_process_env()
@@ -334,8 +335,10 @@ def main(argv=None):
     logger.info(f"Starting distributed training with {world_size} processes")
     logger.info(f"Configuration: epochs={args.epochs}, batch_size={args.batch_size}, lr={args.lr}")
 
-    reg_kw = {"label_smoothing": args.label_smoothing, "z_loss": args.z_loss, "dropout": args.dropout}
-    model_kw = reg_kw if args.model.startswith("gpt2") else ({"image_size": args.image_size} if vit or convnext else {})
+    reg_kw = {"label_smoothing": args.label_smoothing, "z_loss": args.z_loss}
+    if args.model.startswith("gpt2"):
+        reg_kw["dropout"] = args.dropout
+    model_kw = reg_kw if lm else ({"image_size": args.image_size} if vit or convnext else {})
     model = get_model(args.model, **_dtype_kw(args), **model_kw).to(device)
     model = DDP(model, bucket_cap_mb=args.bucket_mb,
                 last_bucket_mb="auto" if args.last_bucket_mb is None else (args.last_bucket_mb or None),
@@ -394,7 +397,7 @@ def main(argv=None):
         epoch_start = time.time()
         train_sampler.set_epoch(epoch)
         train_loss = train_epoch(model, train_loader, optimizer, criterion, device, epoch, rank, args.grad_accum,
-                                 args.max_steps, watchdog, fused_loss=args.model.startswith("gpt2"), mixer=mixer)
+                                 args.max_steps, watchdog, fused_loss=lm, mixer=mixer)
         val_loss, val_accuracy = validate(model, val_loader, criterion, device, num_classes, args.max_steps, watchdog)
 
         metrics = torch.tensor([train_loss, val_loss, val_accuracy], device=device)
