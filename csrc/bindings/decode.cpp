@@ -38,6 +38,48 @@ Tensor attn_decode(const Tensor& qkv_step, Tensor& kc, Tensor& vc, const Tensor&
   return out;
 }
 
+// qkv_step [B, Hq + 2 Hkv, 64] bf16 (unrotated), kc / vc [B, Hkv, Tmax, 64] bf16 (updated in place at row len[b]: the
+// rotated K, the V), len int32 [B], cos / sin fp32 [P, 32] -> [B, Hq * 64]
+Tensor attn_decode_gqa(const Tensor& qkv_step, Tensor& kc, Tensor& vc, const Tensor& len, const Tensor& cos, const Tensor& sin,
+                       int64_t n_kv_head, double scale, int64_t splits, const c10::optional<Tensor>& out_opt) {
+  CHECK_GPU(qkv_step); CHECK_BF16(qkv_step); CHECK_CONTIG(qkv_step);
+  CHECK_GPU(kc); CHECK_BF16(kc); CHECK_CONTIG(kc);
+  CHECK_GPU(vc); CHECK_BF16(vc); CHECK_CONTIG(vc);
+  CHECK_GPU(len); CHECK_CONTIG(len);
+  CHECK_GPU(cos); CHECK_F32(cos); CHECK_CONTIG(cos);
+  CHECK_GPU(sin); CHECK_F32(sin); CHECK_CONTIG(sin);
+  TORCH_CHECK(qkv_step.dim() == 3 && qkv_step.size(2) == 64, "attn_decode_gqa: qkv_step must be [B, Hq + 2 Hkv, 64]");
+  const int64_t B = qkv_step.size(0), Hkv = n_kv_head, Hq = qkv_step.size(1) - 2 * Hkv;
+  TORCH_CHECK(Hkv >= 1 && Hq >= Hkv && Hq % Hkv == 0, "attn_decode_gqa: qkv_step's ", qkv_step.size(1),
+              " heads are not Hq + 2 Hkv with Hq a multiple of Hkv = ", Hkv);
+  TORCH_CHECK(Hq / Hkv <= 16, "attn_decode_gqa: at most 16 query heads per KV head, got ", Hq / Hkv);
+  TORCH_CHECK(kc.dim() == 4 && kc.size(0) == B && kc.size(1) == Hkv && kc.size(3) == 64 && kc.sizes() == vc.sizes(),
+              "attn_decode_gqa: the cache must be [B, Hkv, Tmax, 64] twice");
+  TORCH_CHECK(len.scalar_type() == at::kInt && len.numel() == B, "attn_decode_gqa: len must be int32 [B]");
+  TORCH_CHECK(cos.dim() == 2 && cos.size(0) >= 1 && cos.size(1) == 32 && cos.sizes() == sin.sizes(),
+              "attn_decode_gqa: cos / sin must be [P, 32]");
+  TORCH_CHECK(aligned16(qkv_step) && aligned16(kc) && aligned16(vc) && aligned16(cos) && aligned16(sin),
+              "attn_decode_gqa: 16-byte aligned tensors");
+  const int64_t Tmax = kc.size(2);
+  const int S = splits > 0 ? (int)splits : dpe_attn_decode_splits((int)(B * Hkv), (int)Tmax);
+  TORCH_CHECK(S >= 1 && S <= 1024, "attn_decode_gqa: splits out of range");
+  Tensor out;
+  if (has(out_opt)) {
+    out = *out_opt;
+    CHECK_GPU(out); CHECK_BF16(out); CHECK_CONTIG(out);
+    TORCH_CHECK(out.numel() == B * Hq * 64 && aligned16(out), "attn_decode_gqa: out must be [B, Hq * 64]");
+  } else {
+    out = at::empty({B, Hq * 64}, qkv_step.options());
+  }
+  Tensor ws;
+  if (S > 1) ws = at::empty({dpe_attn_decode_ws_floats((int)(B * Hq), S)}, qkv_step.options().dtype(at::kFloat));
+  CHECK_RC(dpe_attn_decode_gqa(bp(qkv_step), bpm(kc), bpm(vc), (const int32_t*)len.data_ptr(), fp(cos), fp(sin), (int)B, (int)Hq,
+                               (int)Hkv, (int)Tmax, (int)cos.size(0), S, (float)scale, S > 1 ? fp(ws) : nullptr, bpm(out),
+                               cur_stream()),
+           "attn_decode_gqa");
+  return out;
+}
+
 int64_t attn_decode_splits(int64_t BH, int64_t Tmax) { return dpe_attn_decode_splits((int)BH, (int)Tmax); }
 
 int resolve_ksplit(int64_t M, int64_t N, int64_t K, int64_t ksplit) {
@@ -126,6 +168,9 @@ void register_decode(pybind11::module& m) {
   namespace py = pybind11;
   m.def("attn_decode", &attn_decode, py::arg("qkv_step"), py::arg("kc"), py::arg("vc"), py::arg("len"), py::arg("scale"),
         py::arg("splits") = 0, py::arg("out") = py::none(), "single-query attention against the KV cache; stores the step's K/V at row len[b]");
+  m.def("attn_decode_gqa", &attn_decode_gqa, py::arg("qkv_step"), py::arg("kc"), py::arg("vc"), py::arg("len"), py::arg("cos"),
+        py::arg("sin"), py::arg("n_kv_head"), py::arg("scale"), py::arg("splits") = 0, py::arg("out") = py::none(),
+        "grouped-query single-token attention with the step's RoPE fused; stores the rotated K and the V at row len[b]");
   m.def("attn_decode_splits", &attn_decode_splits, py::arg("BH"), py::arg("Tmax"));
   m.def("linear_skinny", &linear_skinny, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("gelu") = false,
         py::arg("out_f32") = false, py::arg("residual") = py::none(), py::arg("out") = py::none(), py::arg("ksplit") = 0,

@@ -569,6 +569,13 @@ int dpe_attn_decode(const uint16_t* qkv_step, uint16_t* kc, uint16_t* vc, const 
   return 0;
 }
 
+// the split merge alone, for a kernel elsewhere that writes the same [BH, S, 66] partials (decode_gqa.hip)
+int dpe_attn_decode_combine(const float* ws, int BH, int S, uint16_t* out, hipStream_t st) {
+  if (BH <= 0 || S < 1 || ws == nullptr) return 1;
+  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(BH), dim3(64), 0, st, ws, S, out);
+  return 0;
+}
+
 int dpe_linear_skinny_ok(int M, int N, int K, int64_t ldx, int64_t ldw) {
   return M >= 1 && M <= 16 && K >= 32 && K % 32 == 0 && N >= 16 && N % 16 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldx >= K &&
          ldw >= K;

@@ -1,4 +1,5 @@
-"""Token ids in, token ids out: continue prompts with a GPT-2 checkpoint written by train.py.
+"""Token ids in, token ids out: continue prompts with a GPT-2 or Llama checkpoint written by train.py
+(``--model``: gpt2, gpt2-tiny, llama-tiny, tinyllama-1.1b).
 
     python -m distributed_pytorch_example_amd.generate --model gpt2-tiny --checkpoint ckpt.pt \\
         --prompt 1,2,3 --prompt 7,8 --max-new-tokens 16 --temperature 0.8 --top-k 40 --top-p 0.95 --seed 0
@@ -52,7 +53,7 @@ def ema_state_dict(model, opt_state: dict):
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m distributed_pytorch_example_amd.generate", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--model", choices=["gpt2", "gpt2-tiny"], default="gpt2")
+    ap.add_argument("--model", choices=["gpt2", "gpt2-tiny", "llama-tiny", "tinyllama-1.1b"], default="gpt2")
     ap.add_argument("--checkpoint", required=True, help="a train.py checkpoint (model_state_dict, optimizer_state_dict)")
     ap.add_argument("--prompt", type=_parse_prompt, action="append", required=True, help="comma-separated token ids; repeat for a batch")
     ap.add_argument("--max-new-tokens", type=int, default=16)

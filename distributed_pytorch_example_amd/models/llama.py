@@ -11,7 +11,14 @@ MLP, no biases, untied LM head by default.  On the GPU every step of a block is 
 * packed documents: Fx.doc_bounds once per batch gives the attention its bounds and RoPE its positions, which
   restart at every document.
 
-Per-op autograd; there is no hand-scheduled fused block and no generation path (KV cache, decode step) yet.
+Per-op autograd; there is no hand-scheduled fused block.
+
+Generation (``generate``, the host loop of models/_generation.py): the prefill runs the padded prompts through the ops
+above and writes each layer's rotated K heads and its V heads into a KVCache of n_kv_head heads; a decode step is
+RMSNorm -> Fx.linear_skinny(c_attn) -> Fx.attn_decode_gqa (csrc/kernels/decode_gqa.hip: the G query heads of a KV head
+in one workgroup on the matrix unit, the rotation of the step's q and k and the cache store fused in) ->
+linear_skinny(attn_proj, residual) -> RMSNorm -> linear_skinny(c_fc) -> Fx.swiglu -> linear_skinny(mlp_proj,
+residual), then ln_f and the LM head; nothing syncs per token and the step replays from a HIP graph.
 """
 from __future__ import annotations
 
@@ -23,6 +30,7 @@ import torch.nn as nn
 
 from ..ops import functional as Fx
 from ..ops.layers import Linear, RMSNorm
+from ._generation import GenerationMixin
 
 HEAD_DIM = 64
 
@@ -82,7 +90,7 @@ class LlamaBlock(nn.Module):
         return Fx.linear_residual(u, self.mlp_proj.weight, None, x)
 
 
-class Llama(nn.Module):
+class Llama(GenerationMixin, nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         if cfg.n_kv_head < 1 or cfg.n_head % cfg.n_kv_head:
@@ -140,3 +148,48 @@ class Llama(nn.Module):
 
     def num_params(self) -> int:
         return sum(p.numel() for p in self.parameters())
+
+    # ------------------------------------------------------------ generation
+    # generate(), its host loop and the HIP-graph replay: _generation.GenerationMixin
+    def _cache_heads(self) -> int:
+        return self.cfg.n_kv_head
+
+    def _head(self, h):
+        """Logits [B, V(p)] of the LM head for h [B, D] (after ln_f)."""
+        V = self.cfg.vocab_size
+        if self.decode_skinny:
+            return Fx.linear_skinny(h, self.head_weight(), pad_rows=((V + 63) // 64 * 64 - V) if h.is_cuda else 0)
+        return Fx.lm_head(h, self.head_weight())
+
+    def _prefill(self, idx, lens, cache):
+        """The padded prompts [B, T] through the training ops; every layer's rotated K heads and its V heads go into
+        the cache head-major, and the LM head runs on row lens[b] - 1 of every sequence only.  Returns logits [B, V(p)]."""
+        B, T = idx.shape
+        Hq, Hkv = self.cfg.n_head, self.cfg.n_kv_head
+        table = (self.rope_cos, self.rope_sin)
+        x = Fx.embedding(idx, self.wte, None)
+        for l, blk in enumerate(self.h):
+            qkv = Fx.rope(blk.c_attn(blk.ln_1(x)), Hq, Hkv, table, inplace=True)
+            kv = qkv.view(B, T, Hq + 2 * Hkv, -1)
+            cache.buf[l, 0, :, :, :T] = kv[:, :, Hq:Hq + Hkv].transpose(1, 2)
+            cache.buf[l, 1, :, :, :T] = kv[:, :, Hq + Hkv:].transpose(1, 2)
+            x = Fx.linear_residual(Fx.causal_attention(qkv, Hq, n_kv_head=Hkv), blk.attn_proj.weight, None, x)
+            x = Fx.linear_residual(Fx.swiglu(blk.c_fc(blk.ln_2(x))), blk.mlp_proj.weight, None, x)
+        last = x[torch.arange(B, device=x.device), lens.long() - 1]  # [B, D]
+        return self._head(self.ln_f(last.unsqueeze(1)).squeeze(1))
+
+    def _decode_step(self, tok, cache):
+        """One token per row through the cache: tok int64 [B] at position cache.len -> logits [B, V(p)].  The position
+        (the table row of the rotation, the cache row) is read from cache.len on the device by Fx.attn_decode_gqa;
+        cache.len is not advanced here and nothing syncs."""
+        B = tok.shape[0]
+        Hq, Hkv = self.cfg.n_head, self.cfg.n_kv_head
+        table = (self.rope_cos, self.rope_sin)
+        x = Fx.embedding(tok.view(B, 1), self.wte, None).view(B, -1)  # fp32 [B, D]
+        for l, blk in enumerate(self.h):
+            qkv = self._proj(blk.ln_1(x), blk.c_attn)
+            a = Fx.attn_decode_gqa(qkv, cache.buf[l, 0], cache.buf[l, 1], cache.len, Hq, Hkv, table)
+            x = self._proj(a, blk.attn_proj, residual=x)
+            u = Fx.swiglu(self._proj(blk.ln_2(x), blk.c_fc))
+            x = self._proj(u, blk.mlp_proj, residual=x)
+        return self._head(self.ln_f(x))

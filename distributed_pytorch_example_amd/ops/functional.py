@@ -1420,6 +1420,43 @@ def attn_decode(qkv_step, kc, vc, lens, n_head: int, scale: Optional[float] = No
     return o.reshape(B, n_head * D)
 
 
+def attn_decode_gqa(qkv_step, kc, vc, lens, n_head: int, n_kv_head: int, table, scale: Optional[float] = None,
+                    splits: int = 0):
+    """``attn_decode`` for grouped-query attention with the step's rotary embedding fused in.  qkv_step
+    [B, (n_head + 2 n_kv_head) * D] is the new token's c_attn output, unrotated (query heads, key heads, value
+    heads); kc / vc [B, n_kv_head, Tmax, D], kc holding rotated keys; ``table`` rope_table's (cos, sin).  With
+    n = lens[b] clamped into [0, Tmax - 1]: the queries and the step's key are rotated by table row n (clamped into the
+    table), row b attends keys 0 .. n of its KV head, and key n -- the rotated K, the V as it is -- is stored into the
+    cache.  Returns [B, n_head * D].  GPU: the HIP kernel (D = 64, at most 16 query heads per KV head; anything else
+    raises); elsewhere the same definition in torch ops on the cache's dtype."""
+    B = qkv_step.shape[0]
+    W = n_head + 2 * n_kv_head
+    if n_kv_head < 1 or n_head % n_kv_head:
+        raise ValueError(f"n_head ({n_head}) must be a multiple of n_kv_head ({n_kv_head})")
+    D, G = qkv_step.numel() // (B * W), n_head // n_kv_head
+    if qkv_step.numel() != B * W * D or table[0].shape[-1] * 2 != D:
+        raise ValueError(f"attn_decode_gqa: qkv_step and the [P, {table[0].shape[-1]}] table do not fit {W} heads")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if qkv_step.is_cuda:
+        if D != 64 or G > 16:
+            raise ValueError(f"attn_decode_gqa: the kernel takes head dim 64 and at most 16 query heads per KV head, got {D} and {G}")
+        return ext().attn_decode_gqa(qkv_step.reshape(B, W, D), kc, vc, lens, table[0], table[1], n_kv_head, float(scale),
+                                     int(splits))
+    Tmax = kc.shape[2]
+    L = lens.long().clamp(0, Tmax - 1)
+    x = _rope_torch(qkv_step.reshape(B, 1, W, D).to(kc.dtype), n_head + n_kv_head, table, L.view(B, 1)).view(B, W, D)
+    q, k, v = x.split([n_head, n_kv_head, n_kv_head], dim=1)
+    rows = torch.arange(B)
+    kc[rows, :, L] = k
+    vc[rows, :, L] = v
+    seen = (torch.arange(Tmax)[None, :] <= L[:, None])[:, None, None, :]  # [B, 1, 1, Tmax]
+    s = torch.einsum("bkgd,bktd->bkgt", q.float().view(B, n_kv_head, G, D), kc.float()) * scale
+    p = torch.softmax(torch.where(seen, s, torch.full_like(s, float("-inf"))), dim=-1)
+    vz = torch.where(seen.squeeze(2).unsqueeze(-1), vc.float(), torch.zeros((), dtype=torch.float32))
+    return torch.einsum("bkgt,bktd->bkgd", p, vz).reshape(B, n_head * D)
+
+
 def linear_skinny(x, weight, bias=None, act: int = ACT_NONE, residual=None, out_f32: bool = False, pad_rows: int = 0,
                   ksplit: int = 0):
     """``linear`` / ``linear_residual`` for M <= 16 rows, no autograd: x [M, K] bf16 against the bf16 shadow of
