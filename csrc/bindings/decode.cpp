@@ -39,9 +39,10 @@ Tensor attn_decode(const Tensor& qkv_step, Tensor& kc, Tensor& vc, const Tensor&
 }
 
 // qkv_step [B, Hq + 2 Hkv, 64] bf16 (unrotated), kc / vc [B, Hkv, Tmax, 64] bf16 (updated in place at row len[b]: the
-// rotated K, the V), len int32 [B], cos / sin fp32 [P, 32] -> [B, Hq * 64]
+// rotated K, the V), len int32 [B], cos / sin fp32 [P, 32] -> [B, Hq * 64].  window W >= 1: sliding-window attention over the
+// keys max(0, len - W + 1) .. len (0 = no window); the default split count is then that of min(Tmax, W) keys.
 Tensor attn_decode_gqa(const Tensor& qkv_step, Tensor& kc, Tensor& vc, const Tensor& len, const Tensor& cos, const Tensor& sin,
-                       int64_t n_kv_head, double scale, int64_t splits, const c10::optional<Tensor>& out_opt) {
+                       int64_t n_kv_head, double scale, int64_t splits, const c10::optional<Tensor>& out_opt, int64_t window) {
   CHECK_GPU(qkv_step); CHECK_BF16(qkv_step); CHECK_CONTIG(qkv_step);
   CHECK_GPU(kc); CHECK_BF16(kc); CHECK_CONTIG(kc);
   CHECK_GPU(vc); CHECK_BF16(vc); CHECK_CONTIG(vc);
@@ -61,7 +62,8 @@ Tensor attn_decode_gqa(const Tensor& qkv_step, Tensor& kc, Tensor& vc, const Ten
   TORCH_CHECK(aligned16(qkv_step) && aligned16(kc) && aligned16(vc) && aligned16(cos) && aligned16(sin),
               "attn_decode_gqa: 16-byte aligned tensors");
   const int64_t Tmax = kc.size(2);
-  const int S = splits > 0 ? (int)splits : dpe_attn_decode_splits((int)(B * Hkv), (int)Tmax);
+  TORCH_CHECK(window >= 0 && window <= INT32_MAX, "attn_decode_gqa: window must be >= 1 (0 = no window), got ", window);
+  const int S = splits > 0 ? (int)splits : dpe_attn_decode_splits((int)(B * Hkv), (int)(window > 0 ? std::min(Tmax, window) : Tmax));
   TORCH_CHECK(S >= 1 && S <= 1024, "attn_decode_gqa: splits out of range");
   Tensor out;
   if (has(out_opt)) {
@@ -75,7 +77,7 @@ Tensor attn_decode_gqa(const Tensor& qkv_step, Tensor& kc, Tensor& vc, const Ten
   if (S > 1) ws = at::empty({dpe_attn_decode_ws_floats((int)(B * Hq), S)}, qkv_step.options().dtype(at::kFloat));
   CHECK_RC(dpe_attn_decode_gqa(bp(qkv_step), bpm(kc), bpm(vc), (const int32_t*)len.data_ptr(), fp(cos), fp(sin), (int)B, (int)Hq,
                                (int)Hkv, (int)Tmax, (int)cos.size(0), S, (float)scale, S > 1 ? fp(ws) : nullptr, bpm(out),
-                               cur_stream()),
+                               (int)window, cur_stream()),
            "attn_decode_gqa");
   return out;
 }
@@ -170,7 +172,9 @@ void register_decode(pybind11::module& m) {
         py::arg("splits") = 0, py::arg("out") = py::none(), "single-query attention against the KV cache; stores the step's K/V at row len[b]");
   m.def("attn_decode_gqa", &attn_decode_gqa, py::arg("qkv_step"), py::arg("kc"), py::arg("vc"), py::arg("len"), py::arg("cos"),
         py::arg("sin"), py::arg("n_kv_head"), py::arg("scale"), py::arg("splits") = 0, py::arg("out") = py::none(),
-        "grouped-query single-token attention with the step's RoPE fused; stores the rotated K and the V at row len[b]");
+        py::arg("window") = 0,
+        "grouped-query single-token attention with the step's RoPE fused; stores the rotated K and the V at row len[b]; "
+        "window W >= 1 attends the last W keys only");
   m.def("attn_decode_splits", &attn_decode_splits, py::arg("BH"), py::arg("Tmax"));
   m.def("linear_skinny", &linear_skinny, py::arg("x"), py::arg("w"), py::arg("bias") = py::none(), py::arg("gelu") = false,
         py::arg("out_f32") = false, py::arg("residual") = py::none(), py::arg("out") = py::none(), py::arg("ksplit") = 0,

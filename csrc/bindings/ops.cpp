@@ -580,6 +580,7 @@ void layernorm_bwd_finalize_group(const std::vector<Tensor>& parts, const std::v
 // causal = false: bidirectional attention over the first seq_len rows (0 = T).
 // n_kv_head > 0: grouped-query attention.  qkv is [B, T, H + 2 * n_kv_head, D] (H query heads, then the key heads, then the
 // value heads); 0 = one K / V head per query head in the [B, T, 3, H, D] layout.
+// window W >= 1: sliding-window causal attention, query i sees the keys max(doc_start[i], i - W + 1) .. i (0 = no window).
 // Which of these combine, and on which kernels: dpe_attn_route (csrc/kernels/attn.hip).
 const int64_t* drop_rng(double p, const c10::optional<Tensor>& rng, int64_t stream, const Tensor& like, uint32_t* thr) {
   TORCH_CHECK(p >= 0.0 && p < 1.0, "attn: dropout_p must be in [0, 1), got ", p);
@@ -602,7 +603,7 @@ struct AttnMode {
   const c10::optional<Tensor>&doc_start, &doc_end;
   double dropout_p;
   const c10::optional<Tensor>& rng;
-  int64_t stream, seq_len, n_kv_head;
+  int64_t stream, seq_len, n_kv_head, window;
 };
 
 // The AttnArgs of a call: the forward's (dout, dqkv null) or the backward's (delta is the caller's to set).  The kernels
@@ -615,6 +616,7 @@ dpe::AttnArgs attn_args(const char* fn, const AttnMode& m, const Tensor& qkv, co
   dpe::AttnArgs a{};
   a.B = (int)B, a.T = (int)T, a.H = (int)H, a.Hkv = (int)m.n_kv_head, a.D = (int)D;
   a.scale = (float)m.scale, a.causal = m.causal, a.seq_len = (int)m.seq_len, a.stream = (uint32_t)m.stream;
+  a.window = (int)std::max<int64_t>(std::min<int64_t>(m.window, INT32_MAX), -1);
   TORCH_CHECK(has(m.doc_start) == has(m.doc_end), fn, ": doc_start and doc_end go together");
   a.doc_start = i32_opt(m.doc_start, B * T, qkv, "attn: doc_start");
   a.doc_end = i32_opt(m.doc_end, B * T, qkv, "attn: doc_end");
@@ -623,7 +625,7 @@ dpe::AttnArgs attn_args(const char* fn, const AttnMode& m, const Tensor& qkv, co
   a.rng = has(m.rng) ? (const int64_t*)m.rng->data_ptr() : nullptr;
   const char* why = "";
   TORCH_CHECK(dpe_attn_route(a, &why) != dpe::AR_NONE, why, " (", fn, ": T=", T, ", H=", H, ", n_kv_head=", m.n_kv_head,
-              ", D=", D, ", seq_len=", m.seq_len, ")");
+              ", D=", D, ", seq_len=", m.seq_len, ", window=", m.window, ")");
   auto tensor = [&](const Tensor& t, at::ScalarType ty, int64_t n, const char* what) {
     TORCH_CHECK(t.is_cuda() && t.device() == qkv.device() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == n,
                 fn, ": ", what, ", contiguous and on qkv's device");
@@ -641,12 +643,12 @@ dpe::AttnArgs attn_args(const char* fn, const AttnMode& m, const Tensor& qkv, co
 std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool causal, const c10::optional<Tensor>& out_,
                              const c10::optional<Tensor>& lse_, const c10::optional<Tensor>& doc_start,
                              const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng,
-                             int64_t stream, int64_t seq_len, int64_t n_kv_head) {
+                             int64_t stream, int64_t seq_len, int64_t n_kv_head, int64_t window) {
   TORCH_CHECK(qkv.dim() >= 3, "attn_fwd: qkv must be [B,T,3,H,D] ([B,T,H+2*n_kv_head,D] with n_kv_head)");
   const int64_t B = qkv.size(0), T = qkv.size(1), D = qkv.size(-1);
   Tensor out = has(out_) ? *out_ : at::empty({B, T, H, D}, qkv.options());
   Tensor lse = has(lse_) ? *lse_ : at::empty({B, H, T}, qkv.options().dtype(at::kFloat));
-  const dpe::AttnArgs a = attn_args("attn_fwd", {H, scale, causal, doc_start, doc_end, dropout_p, rng, stream, seq_len, n_kv_head},
+  const dpe::AttnArgs a = attn_args("attn_fwd", {H, scale, causal, doc_start, doc_end, dropout_p, rng, stream, seq_len, n_kv_head, window},
                                     qkv, out, lse, nullptr, nullptr);
   CHECK_RC(dpe_attn_fwd(a, cur_stream()), "attn_fwd");
   return {out, lse};
@@ -655,9 +657,9 @@ std::vector<Tensor> attn_fwd(const Tensor& qkv, int64_t H, double scale, bool ca
 Tensor attn_bwd(const Tensor& qkv, const Tensor& out, const Tensor& dout, const Tensor& lse, int64_t H, double scale,
                 bool causal, const c10::optional<Tensor>& dqkv_, const c10::optional<Tensor>& doc_start,
                 const c10::optional<Tensor>& doc_end, double dropout_p, const c10::optional<Tensor>& rng, int64_t stream,
-                int64_t seq_len, int64_t n_kv_head) {
+                int64_t seq_len, int64_t n_kv_head, int64_t window) {
   Tensor dqkv = has(dqkv_) ? *dqkv_ : at::empty_like(qkv);
-  dpe::AttnArgs a = attn_args("attn_bwd", {H, scale, causal, doc_start, doc_end, dropout_p, rng, stream, seq_len, n_kv_head},
+  dpe::AttnArgs a = attn_args("attn_bwd", {H, scale, causal, doc_start, doc_end, dropout_p, rng, stream, seq_len, n_kv_head, window},
                               qkv, out, lse, &dout, &dqkv);
   Tensor delta = at::empty({a.B, a.H, a.T}, qkv.options().dtype(at::kFloat));
   a.delta = fp(delta);
@@ -851,11 +853,11 @@ void register_ops(pybind11::module& m) {
   m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("H"), py::arg("scale"), py::arg("causal") = true,
         py::arg("out") = py::none(), py::arg("lse") = py::none(), py::arg("doc_start") = py::none(),
         py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0,
-        py::arg("seq_len") = 0, py::arg("n_kv_head") = 0);
+        py::arg("seq_len") = 0, py::arg("n_kv_head") = 0, py::arg("window") = 0);
   m.def("attn_bwd", &attn_bwd, py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("H"),
         py::arg("scale"), py::arg("causal") = true, py::arg("dqkv") = py::none(), py::arg("doc_start") = py::none(),
         py::arg("doc_end") = py::none(), py::arg("dropout_p") = 0.0, py::arg("rng") = py::none(), py::arg("stream") = 0,
-        py::arg("seq_len") = 0, py::arg("n_kv_head") = 0);
+        py::arg("seq_len") = 0, py::arg("n_kv_head") = 0, py::arg("window") = 0);
   m.def("dropout_add", &dropout_add, py::arg("res"), py::arg("y"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,
         py::arg("out") = py::none(), "fp32 res + dropout(y) (y bf16 or fp32); mask from the device rng state int64[2] (seed, offset) and the stream");
   m.def("dropout_cast", &dropout_cast, py::arg("g"), py::arg("p"), py::arg("rng"), py::arg("stream") = 0,
@@ -865,19 +867,20 @@ void register_ops(pybind11::module& m) {
         "attention on the register-staged kernels instead of the LDS-DMA ones (test switch; default off); returns the "
         "previous setting");
   m.def("attn_route", [](int64_t T, int64_t H, int64_t n_kv_head, int64_t D, bool causal, int64_t seq_len, bool packed,
-                         bool dropout) {
+                         bool dropout, int64_t window) {
           static const int64_t given[2] = {0, 0};  // stands for a tensor that was passed: the route only asks which are null
           dpe::AttnArgs a{};
           a.B = 1, a.T = (int)T, a.H = (int)H, a.Hkv = (int)n_kv_head, a.D = (int)D, a.causal = causal, a.seq_len = (int)seq_len;
           a.doc_start = a.doc_end = packed ? (const int32_t*)given : nullptr;
           a.rng = dropout ? given : nullptr;
           a.thr = dropout ? 128 : 0;
+          a.window = (int)std::max<int64_t>(std::min<int64_t>(window, INT32_MAX), -1);
           static const char* const names[] = {"none", "staged", "dma", "gqa"};
           const char* why = "";
           const int r = dpe_attn_route(a, &why);
           return std::make_tuple(std::string(names[r]), std::string(why));
         }, py::arg("T"), py::arg("H"), py::arg("n_kv_head") = 0, py::arg("D") = 64, py::arg("causal") = true,
-        py::arg("seq_len") = 0, py::arg("packed") = false, py::arg("dropout") = false,
+        py::arg("seq_len") = 0, py::arg("packed") = false, py::arg("dropout") = false, py::arg("window") = 0,
         "the kernel family attn_fwd / attn_bwd would run for these arguments under the current set_attn_staged: "
         "('none' | 'staged' | 'dma' | 'gqa', the reason when 'none'); no tensors, no GPU call");
   m.def("set_gemm_backend", [](int64_t mode) {

@@ -22,6 +22,8 @@ struct AttnArgs {
   int seq_len;               // causal == 0: keys and queries < seq_len (0 = T); out / dqkv rows from there on are zeros
   const int32_t* doc_start;  // packed documents (int32 [B, T], both or neither): query i sees doc_start[i] <= j <= i
   const int32_t* doc_end;
+  int window;                // sliding window W >= 1 (causal, no dropout): query i sees max(doc_start[i], i - W + 1) <= j <= i;
+                             // 0 = no window, W >= T is plain causal attention
   const int64_t* rng;        // dropout on P: device int64[2] (seed, offset)
   uint32_t stream;           // the call site (Philox counter_lo)
   uint32_t thr;              // drop rate thr / 256, 1 .. 255; 0 = no dropout

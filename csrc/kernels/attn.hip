@@ -40,6 +40,8 @@
 // Grouped-query attention (qkv [B, T, Hq + 2 Hkv, 64]: query heads, then key heads, then value heads): GQA entry points
 //   attn_*_gqa_kernel around the bodies of the same three kernels (attn_dma_*_body.h), described at each; every kernel
 //   from before compiles to what it was.
+// Sliding-window attention (query i sees the last W keys of its document): WINDOW instantiations of the LDS-DMA and GQA
+//   kernels, described at each; every kernel from before compiles to what it was.
 #include <type_traits>
 
 #include "attn.h"
@@ -390,19 +392,28 @@ DPE_DEVICE bool drop_keep(uint32_t word, int byte, uint32_t thr) { return ((word
 // query head h reads K / V of head h / (Hq / Hkv).  Only the row stride and the K / V bases change; the G query heads of
 // a group are neighbouring workgroups (bh order), so they meet their shared K / V tiles in L2.
 // The GQA kernels are entry points of their own (attn_*_gqa_kernel) around the same body text (attn_dma_*_body.h).
-template <bool PACKED, bool DROP, bool BIDIR = false>
+// WINDOW (sliding-window causal attention; no DROP, no BIDIR; with or without PACKED and GQA): query i sees the keys
+// max(doc_start[i], i - W + 1) .. i.  The lower bound is the packed path's, so the walk is the packed one with other
+// numbers: the workgroup starts at the tile of its first query's window edge, a wave skips the tiles below its own, the
+// tiles that hold a key below the wave's last query's edge (at most two) take the both-bounds path, the ones between
+// the edge and the diagonal the mask-free path.  Without PACKED the lane's bound is computed from its query index and
+// doc_start is never read.  A workgroup walks about W / 64 + 2 tiles instead of its whole causal prefix.  Every row keeps
+// its diagonal key; a wave can meet a tile in which some rows see nothing, which the both-bounds path covers.  W chooses
+// loop bounds and masks only, never an address.  The launcher sends W >= T to the instantiations without the switch.
+template <bool PACKED, bool DROP, bool BIDIR = false, bool WINDOW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_fwd_dma_kernel(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse2, int B, int T, int H,
     float sl2, const int* __restrict__ doc_start, AttnDrop dr, int L) {
   constexpr bool GQA = false;
   [[maybe_unused]] const int Hkv = H;
+  [[maybe_unused]] const int window = L;  // WINDOW: the launcher passes the window where BIDIR takes its key bound
 #include "attn_dma_fwd_body.h"
 }
 DPE_NO_PK_F32_BEGIN
-template <bool PACKED>
+template <bool PACKED, bool WINDOW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void attn_fwd_gqa_kernel(
     const uint16_t* __restrict__ qkv, uint16_t* __restrict__ out, float* __restrict__ lse2, int B, int T, int Hq, int Hkv,
-    float sl2, const int* __restrict__ doc_start) {
+    float sl2, const int* __restrict__ doc_start, int window) {
   constexpr bool GQA = true, DROP = false, BIDIR = false;
   const int H = Hq;
   [[maybe_unused]] const AttnDrop dr{};
@@ -602,7 +613,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const uint16_t* __restric
 // puts head j + 1's first tile in the other buffer).  kf / vf are loaded once and dk / dv stay in the same registers
 // over all G heads: the group sum is the fp32 accumulation itself, rounded to bf16 once at the store -- no atomics, no
 // per-query-head dK / dV and no reduction pass.
-template <bool PACKED, bool DROP, bool BIDIR = false>
+// WINDOW: key j is seen by the queries j .. j + W - 1, so the query-tile loop ends at the tile of query
+// min(T - 1, k0 + 127 + W - 1) (per wave: of kw0 + 31 + W - 1), also under PACKED's end.  A tile whose last query's window
+// edge lies behind the wave's first key masks on both bounds (i - W + 1 <= j computed per element, beside the staged
+// doc_start when PACKED); the tiles between the wave's diagonal and that one are mask-free.  GQA: every head of the group
+// walks the same shortened tile range, and the flattened walk restarts each head at the key tile's own query tile.
+template <bool PACKED, bool DROP, bool BIDIR = false, bool WINDOW = false>
 __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout,
                                                        const float* __restrict__ lse2, const float* __restrict__ delta,
                                                        uint16_t* __restrict__ dqkv, int B, int T, int H, float sl2,
@@ -610,14 +626,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dma_kernel(const uint16_t* __res
                                                        const int* __restrict__ doc_end, AttnDrop dr, int L) {
   constexpr bool GQA = false;
   [[maybe_unused]] const int Hkv = H;
+  [[maybe_unused]] const int window = L;  // WINDOW: the launcher passes the window where BIDIR takes its key bound
 #include "attn_dma_dkv_body.h"
 }
 DPE_NO_PK_F32_BEGIN
-template <bool PACKED>
+template <bool PACKED, bool WINDOW = false>
 __global__ __launch_bounds__(256) void attn_bwd_gqa_kernel(
     const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ dout, const float* __restrict__ lse2,
     const float* __restrict__ delta, uint16_t* __restrict__ dqkv, int B, int T, int Hq, int Hkv, float sl2, float scale,
-    const int* __restrict__ doc_start, const int* __restrict__ doc_end) {
+    const int* __restrict__ doc_start, const int* __restrict__ doc_end, int window) {
   constexpr bool GQA = true, DROP = false, BIDIR = false;
   const int H = Hq;
   [[maybe_unused]] const AttnDrop dr{};
@@ -781,7 +798,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const uint16_t* __rest
 // BIDIR: the forward's walk (attn_fwd_dma_kernel) -- key tiles 0 .. ceil(L / 64) - 1, the last one with P and dS of the
 // keys >= L selected to 0 after the exp2.  dQ rows >= L are exact zeros and delta rows >= L are 0.0f.
 // GQA: the forward's addressing (attn_fwd_dma_body) -- K / V of head h / (Hq / Hkv), the grouped row stride.
-template <bool PACKED, bool DROP, bool BIDIR = false>
+template <bool PACKED, bool DROP, bool BIDIR = false, bool WINDOW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAVES))) void attn_bwd_dq_dma_kernel(const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o,
                                                           const uint16_t* __restrict__ dout,
                                                           const float* __restrict__ lse2, float* __restrict__ delta,
@@ -790,14 +807,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAV
                                                           int L) {
   constexpr bool GQA = false;
   [[maybe_unused]] const int Hkv = H;
+  [[maybe_unused]] const int window = L;  // WINDOW: the launcher passes the window where BIDIR takes its key bound
 #include "attn_dma_dq_body.h"
 }
 DPE_NO_PK_F32_BEGIN
-template <bool PACKED>
+template <bool PACKED, bool WINDOW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ATTN_DQ_WAVES))) void attn_bwd_dq_gqa_kernel(
     const uint16_t* __restrict__ qkv, const uint16_t* __restrict__ o, const uint16_t* __restrict__ dout,
     const float* __restrict__ lse2, float* __restrict__ delta, uint16_t* __restrict__ dqkv, int B, int T, int Hq, int Hkv,
-    float sl2, float scale, const int* __restrict__ doc_start) {
+    float sl2, float scale, const int* __restrict__ doc_start, int window) {
   constexpr bool GQA = true, DROP = false, BIDIR = false;
   const int H = Hq;
   [[maybe_unused]] const AttnDrop dr{};
@@ -821,14 +839,19 @@ extern "C" int dpe_set_attn_staged(int on) {
 
 // The mode matrix (attn.h).  Packed documents, dropout, the bidirectional mask and grouped K / V heads exist on the
 // LDS-DMA kernels only: where those cannot run, such a call is an error and a plain causal one takes the register-staged
-// kernels.  Packed documents combine with dropout and with grouped heads; nothing else combines.
+// kernels.  Packed documents combine with dropout and with grouped heads, a window with packed documents and with grouped
+// heads; nothing else combines.
 extern "C" int dpe_attn_route(const AttnArgs& a, const char** why) {
   const bool gqa = a.Hkv != 0, bidir = !a.causal, packed = a.doc_start || a.doc_end, drop = a.thr != 0;
   // one sequence's qkv rows (dO has fewer) must fit the DMA kernels' 32-bit buffer range
   const int64_t heads = gqa ? (int64_t)a.H + 2 * (int64_t)a.Hkv : 3 * (int64_t)a.H;
   const bool dma = !g_attn_staged && (int64_t)a.T * heads * AD * 2 < (1LL << 31);
   const char* no = nullptr;
-  if (gqa && (a.Hkv < 1 || a.H < a.Hkv || a.H % a.Hkv != 0)) no = "attn: H must be a multiple of n_kv_head";
+  if (a.window < 0) no = "attn: window must be >= 1 (0 = no window)";
+  else if (a.window && (bidir || a.seq_len != 0)) no = "attn: window goes with causal=True and no seq_len";
+  else if (a.window && (drop || a.rng)) no = "attn: window takes no dropout arguments";
+  else if (a.window && !dma) no = "attn: window runs on the LDS-DMA kernels only (staged switch, or T * heads >= 2^31 bytes)";
+  else if (gqa && (a.Hkv < 1 || a.H < a.Hkv || a.H % a.Hkv != 0)) no = "attn: H must be a multiple of n_kv_head";
   else if (gqa && (bidir || a.seq_len != 0)) no = "attn: n_kv_head goes with causal=True and no seq_len";
   else if (gqa && (drop || a.rng)) no = "attn: n_kv_head takes no dropout arguments";
   else if (a.D != AD) no = "attn: head dim 64 supported";
@@ -850,28 +873,34 @@ extern "C" int dpe_attn_route(const AttnArgs& a, const char** why) {
   return gqa ? AR_GQA : dma ? AR_DMA : AR_STAGED;
 }
 
-// f(PACKED, DROP, BIDIR) with the call's three template switches as std::bool_constant values: the five combinations
-// the route lets through (GQA uses PACKED alone), so nothing else is instantiated.
+// A window that cuts nothing (W >= T) is plain causal attention: it takes the instantiations without the switch.
+static bool attn_windowed(const AttnArgs& a) { return a.window > 0 && a.window < a.T; }
+
+// f(PACKED, DROP, BIDIR, WINDOW) with the call's four template switches as std::bool_constant values: the seven
+// combinations the route lets through (GQA uses PACKED and WINDOW alone), so nothing else is instantiated.
 template <class F>
 static void with_mode(const AttnArgs& a, F f) {
   constexpr std::true_type y{};
   constexpr std::false_type n{};
-  const bool packed = a.doc_start != nullptr, drop = a.thr != 0;
-  if (!a.causal) f(n, n, y);
-  else if (packed && drop) f(y, y, n);
-  else if (packed) f(y, n, n);
-  else if (drop) f(n, y, n);
-  else f(n, n, n);
+  const bool packed = a.doc_start != nullptr, drop = a.thr != 0, win = attn_windowed(a);
+  if (!a.causal) f(n, n, y, n);
+  else if (packed && drop) f(y, y, n, n);
+  else if (packed && win) f(y, n, n, y);
+  else if (packed) f(y, n, n, n);
+  else if (drop) f(n, y, n, n);
+  else if (win) f(n, n, n, y);
+  else f(n, n, n, n);
 }
 
-// What every launch of a call shares: scale * log2(e), the dropout block, the bidirectional key bound (0 = causal).
+// What every launch of a call shares: scale * log2(e), the dropout block, the bidirectional key bound (0 = causal), the
+// window (0 = none).  The LDS-DMA kernels take the window in L's place (the two modes never meet).
 struct AttnLaunch {
   float sl2;
   AttnDrop dr;
-  int L;
+  int L, W;
   explicit AttnLaunch(const AttnArgs& a)
       : sl2(a.scale * 1.4426950408889634f), dr(a.thr ? AttnDrop{a.rng, a.stream, a.thr} : AttnDrop{}),
-        L(a.causal ? 0 : a.seq_len ? a.seq_len : a.T) {}
+        L(a.causal ? 0 : a.seq_len ? a.seq_len : a.T), W(attn_windowed(a) ? a.window : 0) {}
 };
 
 extern "C" int dpe_attn_fwd(const AttnArgs& a, hipStream_t st) {
@@ -883,14 +912,14 @@ extern "C" int dpe_attn_fwd(const AttnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(attn_fwd_kernel, grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T, a.H, l.sl2);
     return 0;
   }
-  with_mode(a, [&](auto P, auto Dr, auto Bi) {
-    constexpr bool PACKED = decltype(P)::value, DROP = decltype(Dr)::value, BIDIR = decltype(Bi)::value;
+  with_mode(a, [&](auto P, auto Dr, auto Bi, auto Wn) {
+    constexpr bool PACKED = decltype(P)::value, DROP = decltype(Dr)::value, BIDIR = decltype(Bi)::value, WINDOW = decltype(Wn)::value;
     if (route == AR_GQA)
-      hipLaunchKernelGGL(attn_fwd_gqa_kernel<PACKED>, grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T, a.H, a.Hkv, l.sl2,
-                         a.doc_start);
+      hipLaunchKernelGGL((attn_fwd_gqa_kernel<PACKED, WINDOW>), grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T, a.H, a.Hkv,
+                         l.sl2, a.doc_start, l.W);
     else
-      hipLaunchKernelGGL((attn_fwd_dma_kernel<PACKED, DROP, BIDIR>), grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T, a.H,
-                         l.sl2, a.doc_start, l.dr, l.L);
+      hipLaunchKernelGGL((attn_fwd_dma_kernel<PACKED, DROP, BIDIR, WINDOW>), grid, blk, 0, st, a.qkv, a.out, a.lse, a.B, a.T,
+                         a.H, l.sl2, a.doc_start, l.dr, WINDOW ? l.W : l.L);
   });
   return 0;
 }
@@ -908,18 +937,18 @@ extern "C" int dpe_attn_bwd(const AttnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(attn_bwd_kernel, gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T, a.H, l.sl2, a.scale);
     return 0;
   }
-  with_mode(a, [&](auto P, auto Dr, auto Bi) {
-    constexpr bool PACKED = decltype(P)::value, DROP = decltype(Dr)::value, BIDIR = decltype(Bi)::value;
+  with_mode(a, [&](auto P, auto Dr, auto Bi, auto Wn) {
+    constexpr bool PACKED = decltype(P)::value, DROP = decltype(Dr)::value, BIDIR = decltype(Bi)::value, WINDOW = decltype(Wn)::value;
     if (route == AR_GQA) {
-      hipLaunchKernelGGL(attn_bwd_dq_gqa_kernel<PACKED>, gq, blk, 0, st, a.qkv, a.out, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T,
-                         a.H, a.Hkv, l.sl2, a.scale, a.doc_start);
-      hipLaunchKernelGGL(attn_bwd_gqa_kernel<PACKED>, gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T, a.H,
-                         a.Hkv, l.sl2, a.scale, a.doc_start, a.doc_end);
+      hipLaunchKernelGGL((attn_bwd_dq_gqa_kernel<PACKED, WINDOW>), gq, blk, 0, st, a.qkv, a.out, a.dout, a.lse, a.delta, a.dqkv,
+                         a.B, a.T, a.H, a.Hkv, l.sl2, a.scale, a.doc_start, l.W);
+      hipLaunchKernelGGL((attn_bwd_gqa_kernel<PACKED, WINDOW>), gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta, a.dqkv, a.B, a.T,
+                         a.H, a.Hkv, l.sl2, a.scale, a.doc_start, a.doc_end, l.W);
     } else {
-      hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<PACKED, DROP, BIDIR>), gq, blk, 0, st, a.qkv, a.out, a.dout, a.lse, a.delta,
-                         a.dqkv, a.B, a.T, a.H, l.sl2, a.scale, a.doc_start, l.dr, l.L);
-      hipLaunchKernelGGL((attn_bwd_dma_kernel<PACKED, DROP, BIDIR>), gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta, a.dqkv, a.B,
-                         a.T, a.H, l.sl2, a.scale, a.doc_start, a.doc_end, l.dr, l.L);
+      hipLaunchKernelGGL((attn_bwd_dq_dma_kernel<PACKED, DROP, BIDIR, WINDOW>), gq, blk, 0, st, a.qkv, a.out, a.dout, a.lse,
+                         a.delta, a.dqkv, a.B, a.T, a.H, l.sl2, a.scale, a.doc_start, l.dr, WINDOW ? l.W : l.L);
+      hipLaunchKernelGGL((attn_bwd_dma_kernel<PACKED, DROP, BIDIR, WINDOW>), gk, blk, 0, st, a.qkv, a.dout, a.lse, a.delta,
+                         a.dqkv, a.B, a.T, a.H, l.sl2, a.scale, a.doc_start, a.doc_end, l.dr, WINDOW ? l.W : l.L);
     }
   });
   return 0;

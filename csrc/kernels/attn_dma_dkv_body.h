@@ -1,10 +1,11 @@
 // The body of the LDS-DMA dK / dV kernel: included (not compiled alone) inside each of its entry points in attn.hip, which
-// set the scope it reads -- PACKED, DROP, BIDIR, GQA (constexpr bool) and qkv, dout, lse2, delta, dqkv, B, T, H, sl2, scale, doc_start, doc_end, dr, L, Hkv.
+// set the scope it reads -- PACKED, DROP, BIDIR, GQA, WINDOW (constexpr bool) and qkv, dout, lse2, delta, dqkv, B, T, H, sl2, scale, doc_start, doc_end, dr, L, Hkv, window.
 // Text inclusion, not a shared device function: the entry points from before GQA then compile to exactly the
 // instructions they had (an inlined body function changes the schedule), and the GQA entry points can carry their own
 // target attribute (DPE_NO_PK_F32).
   static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
   static_assert(!GQA || (!DROP && !BIDIR), "grouped K / V heads have no dropout or bidirectional form");
+  static_assert(!WINDOW || (!DROP && !BIDIR), "the sliding window has no dropout or bidirectional form");
   // per buffer: Qk Qm dOk dOm (8 KB each) + lse, delta (512 B) (+ packed: doc_start, 256 B)
   constexpr int BUF = 4 * 8192 + 512 + (PACKED ? 256 : 0);
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -110,6 +111,12 @@
     qend = min(max((max(ew, 1) - 1) / AQ + 1, qs + 1), nqt);
     if (live) qhiw = (max(__builtin_amdgcn_readfirstlane(deb[k0w + 31]), 1) - 1) / AQ;
   }
+  // window: key j is seen by the queries j .. j + window - 1 (a query's lower bound is an upper bound on the query per key),
+  // so the workgroup's loop ends at the tile of its last key's last query, a wave's at its own
+  if constexpr (WINDOW) {
+    qend = min(qend, min(T - 1, kt * BKW + BKW - 1 + window - 1) / AQ + 1);
+    qhiw = min(qhiw, (k0w + 31 + window - 1) / AQ);
+  }
   // GQA: tiles of the flattened (head, query tile) walk that are still to be computed
   [[maybe_unused]] int left = GQA ? (H / Hkv) * (qend - qs) : 0;
   dma_tile(qs, 0);
@@ -181,7 +188,7 @@
       for (int mt = 0; mt < 4; ++mt) {
         const f32x4 l4 = *(const f32x4*)(sl + 16 * mt + 4 * g);
         [[maybe_unused]] u32x4 d4;
-        if constexpr (MK == 2) d4 = *(const u32x4*)(base + 4 * 8192 + 512 + 4 * (16 * mt + 4 * g));
+        if constexpr (MK == 2 && PACKED) d4 = *(const u32x4*)(base + 4 * 8192 + 512 + 4 * (16 * mt + 4 * g));
         [[maybe_unused]] f32x4 ndd;
         if constexpr (DROP) ndd = *(const f32x4*)(snd + 16 * mt + 4 * g);
 #pragma unroll
@@ -193,7 +200,11 @@
               if (k0w + 16 * r + li > qt * AQ + 16 * mt + 4 * g + e) p = 0.f;
             if constexpr (MK == 2) {  // the key is behind the query, or the query's document starts behind the key
               const int key = k0w + 16 * r + li;
-              p = ((key > qt * AQ + 16 * mt + 4 * g + e) | ((int)d4[e] > key)) ? 0.f : p;
+              if constexpr (PACKED) p = ((key > qt * AQ + 16 * mt + 4 * g + e) | ((int)d4[e] > key)) ? 0.f : p;
+              if constexpr (WINDOW) {  // the window's edge of the query is behind the key (with the causal bound when not packed)
+                const int q = qt * AQ + 16 * mt + 4 * g + e;
+                p = ((!PACKED & (key > q)) | (q - window + 1 > key)) ? 0.f : p;
+              }
             }
             if constexpr (DROP) {
               const bool keep = drop_keep(dm[r][mt], e, dr.thr);
@@ -228,10 +239,12 @@
       }
     };
     // query tiles whose first query is past the wave's last key need no causal mask
-    if constexpr (PACKED) {
+    if constexpr (PACKED || WINDOW) {
       if (live && qt >= qtw && qt <= qhiw) {
-        // doc_start is monotone: the tile's last query has the largest
-        const int dlast = __builtin_amdgcn_readfirstlane(((const int*)(smem + cur * BUF + 4 * 8192 + 512))[AQ - 1]);
+        // doc_start is monotone: the tile's last query has the largest (and the latest window edge)
+        int dlast = 0;
+        if constexpr (PACKED) dlast = __builtin_amdgcn_readfirstlane(((const int*)(smem + cur * BUF + 4 * 8192 + 512))[AQ - 1]);
+        if constexpr (WINDOW) dlast = max(dlast, qt * AQ + AQ - window);
         if (dlast > k0w) compute(smem + cur * BUF, std::integral_constant<int, 2>{});
         else if (qt * AQ >= k0w + 31) compute(smem + cur * BUF, std::integral_constant<int, 0>{});
         else compute(smem + cur * BUF, std::integral_constant<int, 1>{});

@@ -1,10 +1,11 @@
 // The body of the LDS-DMA dQ kernel: included (not compiled alone) inside each of its entry points in attn.hip, which
-// set the scope it reads -- PACKED, DROP, BIDIR, GQA (constexpr bool) and qkv, o, dout, lse2, delta, dqkv, B, T, H, sl2, scale, doc_start, dr, L, Hkv.
+// set the scope it reads -- PACKED, DROP, BIDIR, GQA, WINDOW (constexpr bool) and qkv, o, dout, lse2, delta, dqkv, B, T, H, sl2, scale, doc_start, dr, L, Hkv, window.
 // Text inclusion, not a shared device function: the entry points from before GQA then compile to exactly the
 // instructions they had (an inlined body function changes the schedule), and the GQA entry points can carry their own
 // target attribute (DPE_NO_PK_F32).
   static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
   static_assert(!GQA || (!DROP && !BIDIR), "grouped K / V heads have no dropout or bidirectional form");
+  static_assert(!WINDOW || (!DROP && !BIDIR), "the sliding window has no dropout or bidirectional form");
   // per buffer: K (two d-halves, K-contig) 8K | V (same) 8K | K permuted-row image 8K
   constexpr int KI = 0, VI = 2 * AKV * 64, KP = 4 * AKV * 64, STG = KP + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
@@ -76,6 +77,14 @@
       ds[0] = dsb[q0w + li];
       ds[1] = dsb[q0w + 16 + li];
     }
+  }
+  // window: the forward's walk (attn_dma_fwd_body) -- the bounds also hold i - window + 1, computed, not loaded
+  if constexpr (WINDOW) {
+    kt0 = max(kt0, max(qt * FQ - window + 1, 0) / AKV);
+    klo = max(klo, max(q0w - window + 1, 0) / AKV);
+    dshi = max(dshi, q0w + 32 - window);
+    ds[0] = max(ds[0], q0w + li - window + 1);
+    ds[1] = max(ds[1], q0w + 16 + li - window + 1);
   }
 
   // the sequence's qkv rows from K of head h on: one buffer resource, tile advance in soffset
@@ -178,7 +187,7 @@
         for (int r = 0; r < 2; ++r) acc[r][d] = MFMA(a1, dd[r][1], MFMA(a0, dd[r][0], acc[r][d]));
       }
     };
-    if constexpr (PACKED) {
+    if constexpr (PACKED || WINDOW) {
       if (kt >= klo && kt <= ktw) {
         if (kt * AKV < dshi) compute(smem + cur * STG, std::integral_constant<int, 2>{});
         else if (kt < kd) compute(smem + cur * STG, std::integral_constant<int, 0>{});

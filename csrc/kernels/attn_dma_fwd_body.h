@@ -1,10 +1,11 @@
 // The body of the LDS-DMA forward kernel: included (not compiled alone) inside each of its entry points in attn.hip, which
-// set the scope it reads -- PACKED, DROP, BIDIR, GQA (constexpr bool) and qkv, out, lse2, B, T, H, sl2, doc_start, dr, L, Hkv.
+// set the scope it reads -- PACKED, DROP, BIDIR, GQA, WINDOW (constexpr bool) and qkv, out, lse2, B, T, H, sl2, doc_start, dr, L, Hkv, window.
 // Text inclusion, not a shared device function: the entry points from before GQA then compile to exactly the
 // instructions they had (an inlined body function changes the schedule), and the GQA entry points can carry their own
 // target attribute (DPE_NO_PK_F32).
   static_assert(!BIDIR || (!PACKED && !DROP), "the bidirectional mode has no packed or dropout form");
   static_assert(!GQA || (!DROP && !BIDIR), "grouped K / V heads have no dropout or bidirectional form");
+  static_assert(!WINDOW || (!DROP && !BIDIR), "the sliding window has no dropout or bidirectional form");
   constexpr int KB = 2 * AKV * 64, STG = KB + AKV * 128;
   __shared__ __attribute__((aligned(16))) char smem[2 * STG];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
@@ -29,6 +30,16 @@
       ds[0] = dsb[q0w + li];
       ds[1] = dsb[q0w + 16 + li];
     }
+  }
+  // window: query i's lower bound is also i - window + 1.  It is affine in the lane's query, so the pure-window form
+  // loads nothing; the workgroup starts at its first query's window edge, a wave at its own, and only the tiles that
+  // hold a key below the wave's last query's edge (at most two) take the both-bounds path
+  if constexpr (WINDOW) {
+    kt0 = max(kt0, max(qt * FQ - window + 1, 0) / AKV);
+    klo = max(klo, max(q0w - window + 1, 0) / AKV);
+    dshi = max(dshi, q0w + 32 - window);
+    ds[0] = max(ds[0], q0w + li - window + 1);
+    ds[1] = max(ds[1], q0w + 16 + li - window + 1);
   }
   if constexpr (BIDIR) {
     if (qt * FQ >= L) {  // every query of the workgroup is padding (workgroup-uniform: no barrier is left behind)
@@ -233,7 +244,7 @@
     constexpr int cur = decltype(bufc)::value;
     const bool more = kt + 1 < nkt;
     if (more) dma_tile(kt + 1, smem + (cur ^ 1) * STG);  // read last in step kt - 1, before its barrier
-    if constexpr (PACKED) {
+    if constexpr (PACKED || WINDOW) {
       if (kt >= klo && kt <= ktw) {
         if (kt * AKV < dshi) compute(kt, smem + cur * STG, std::integral_constant<int, 2>{});
         else if (kt < kd) compute(kt, smem + cur * STG, std::integral_constant<int, 0>{});

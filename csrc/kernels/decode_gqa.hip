@@ -6,7 +6,8 @@
 // [B, Hkv, Tmax, 64], kc holding rotated keys.  With n = clamp(len[b], 0, Tmax - 1): the G queries of a group and the
 // step's key are rotated by table row clamp(n, 0, P - 1) (rotate-half, rope_kernel's expression, fp32, one RNE
 // rounding); row b attends keys 0 .. n, key n being the step's rotated K and unrotated V, which split 0's workgroup
-// also stores into cache row n.  No workgroup loads a cache row >= n.
+// also stores into cache row n.  No workgroup loads a cache row >= n.  window = W >= 1 (sliding-window attention, 0 =
+// none): row b attends keys max(0, n - W + 1) .. n, and no workgroup loads a cache row below that either.
 //
 // Work split.  Grid (S, B Hkv): one workgroup of 4 waves serves one KV head and all G of its query heads, so every
 // K / V byte is loaded once for the group.  The split's key range is cut into 32-key tiles that go round-robin to
@@ -110,7 +111,8 @@ __global__ __launch_bounds__(64 * GD_NW) void attn_decode_gqa_kernel(const uint1
                                                                      const int32_t* __restrict__ lens,
                                                                      const float* __restrict__ cs, const float* __restrict__ sn,
                                                                      int Hq, int Hkv, int Tmax, int P, int S, float sl2,
-                                                                     float* __restrict__ ws, uint16_t* __restrict__ out) {
+                                                                     float* __restrict__ ws, uint16_t* __restrict__ out,
+                                                                     int window) {
   __shared__ __attribute__((aligned(16))) char smem[GD_NW * GD_RING * GD_SLOT];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, li = lane & 15;
   const int s = blockIdx.x, bk = blockIdx.y, b = bk / Hkv, kvh = bk - b * Hkv;
@@ -158,8 +160,13 @@ __global__ __launch_bounds__(64 * GD_NW) void attn_decode_gqa_kernel(const uint1
     *(u32x4*)(dst + 32) = a1;
   }
 
+  // window: the keys below klo = max(0, n - window + 1) are outside it; the splits share klo .. n, so no cache row below
+  // klo is loaded (a window chooses loop bounds, never an address beyond the rows 0 .. n)
+  const int klo = window > 0 && n + 1 > window ? n + 1 - window : 0;
   int j0, j1;
-  gd_split_range(n + 1, S, s, j0, j1);
+  gd_split_range(n + 1 - klo, S, s, j0, j1);
+  j0 += klo;
+  j1 += klo;
   const int jend = j1 < n ? j1 : n;  // keys below come from the cache; from jend on a slot is the step's row
   const int ntile = (j1 - j0 + GD_TK - 1) / GD_TK;
   char* ring = smem + w * (GD_RING * GD_SLOT);
@@ -292,11 +299,12 @@ __global__ __launch_bounds__(64 * GD_NW) void attn_decode_gqa_kernel(const uint1
 
 extern "C" int dpe_attn_decode_gqa(const uint16_t* qkv_step, uint16_t* kc, uint16_t* vc, const int32_t* len, const float* cos,
                                    const float* sin, int B, int Hq, int Hkv, int Tmax, int P, int S, float scale, float* ws,
-                                   uint16_t* out, hipStream_t st) {
+                                   uint16_t* out, int window, hipStream_t st) {
+  if (window < 0) return 1;
   if (B <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || Hq / Hkv > 16 || Tmax <= 0 || Tmax > (1 << 24) || P <= 0) return 1;
   if (S < 1 || S > 65535 || (int64_t)B * Hkv > 65535 || (S > 1 && ws == nullptr)) return 1;
   hipLaunchKernelGGL(attn_decode_gqa_kernel, dim3(S, B * Hkv), dim3(64 * GD_NW), 0, st, qkv_step, kc, vc, len, cos, sin, Hq, Hkv,
-                     Tmax, P, S, scale * GD_L2E, ws, out);
+                     Tmax, P, S, scale * GD_L2E, ws, out, window);
   if (S > 1) return dpe_attn_decode_combine(ws, B * Hq, S, out, st);
   return 0;
 }

@@ -199,10 +199,11 @@ int dpe_attn_decode_combine(const float* ws, int BH, int S, uint16_t* out, hipSt
 // ---- decode_gqa.hip
 // Hq = G Hkv query heads (1 <= G <= 16) of one new token against kc / vc [B, Hkv, Tmax, 64]; qkv_step [B, Hq + 2 Hkv, 64]
 // unrotated; cos / sin fp32 [P, 32], row clamp(len, 0, P - 1) rotates the queries and the step's key, which is stored
-// rotated at cache row len[b] (V as it is); ws: dpe_attn_decode_ws_floats(B * Hq, S) floats; out [B, Hq * 64]
+// rotated at cache row len[b] (V as it is); ws: dpe_attn_decode_ws_floats(B * Hq, S) floats; out [B, Hq * 64];
+// window W >= 1: row b attends keys max(0, len - W + 1) .. len only (0 = all of 0 .. len)
 int dpe_attn_decode_gqa(const uint16_t* qkv_step, uint16_t* kc, uint16_t* vc, const int32_t* len, const float* cos,
                         const float* sin, int B, int Hq, int Hkv, int Tmax, int P, int S, float scale, float* ws, uint16_t* out,
-                        hipStream_t st);
+                        int window, hipStream_t st);
 // y[M, N] = x[M, K] w[N, K]^T, M <= 16, K % 32 == 0, N % 16 == 0, row strides % 8 == 0.  bf16 out (+ bias, GELU) or
 // fp32 out (+ bias, + fp32 residual that may alias y).  ksplit > 1: ws of ksplit * M * N floats.
 int dpe_linear_skinny_ok(int M, int N, int K, int64_t ldx, int64_t ldw);

@@ -65,11 +65,15 @@ def main(argv=None) -> int:
     ap.add_argument("--graph", action="store_true", help="replay the decode step from a captured HIP graph (GPU)")
     ap.add_argument("--ema", action="store_true", help="generate from the optimizer state's averaged weights")
     ap.add_argument("--device", default=None, help="default: cuda when there is one")
+    ap.add_argument("--sliding-window", type=int, default=None,
+                    help="llama models: the sliding attention window the checkpoint was trained with (0 = off)")
     args = ap.parse_args(argv)
+    if args.sliding_window is not None and (not args.model.startswith(("llama", "tinyllama")) or args.sliding_window < 0):
+        ap.error("--sliding-window needs a llama model and a window >= 1 (0 = off)")
 
     dev = torch.device(args.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
-    model = get_model(args.model)
+    model = get_model(args.model, **({"sliding_window": args.sliding_window} if args.sliding_window else {}))
     model.load_state_dict(ckpt["model_state_dict"])
     if args.ema:
         ema = ema_state_dict(model, ckpt.get("optimizer_state_dict") or {})

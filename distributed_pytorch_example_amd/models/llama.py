@@ -49,6 +49,7 @@ class LlamaConfig:
     tie_embeddings: bool = False
     label_smoothing: float = 0.0  # training-loss regularisers, inside the fused LM-head CE (Fx.lm_head_ce)
     z_loss: float = 0.0
+    sliding_window: int = 0  # W >= 1: every layer's query i attends the keys i - W + 1 .. i only (0 = all of 0 .. i)
 
     @classmethod
     def tiny(cls, **kw):
@@ -68,6 +69,7 @@ class LlamaBlock(nn.Module):
         super().__init__()
         d = cfg.n_embd
         self.n_head, self.n_kv_head = cfg.n_head, cfg.n_kv_head
+        self.window = cfg.sliding_window or None
         self.ln_1 = RMSNorm(d, cfg.rms_eps)
         self.c_attn = Linear(d, (cfg.n_head + 2 * cfg.n_kv_head) * HEAD_DIM, bias=False)  # rows: Q heads, K heads, V heads
         self.attn_proj = Linear(cfg.n_head * HEAD_DIM, d, bias=False)
@@ -84,7 +86,7 @@ class LlamaBlock(nn.Module):
         """``table``: Fx.rope_table's (cos, sin); ``doc``: Fx.doc_bounds' (doc_start, doc_end, pos) or None."""
         qkv = self.c_attn(self.ln_1(x))
         qkv = Fx.rope(qkv, self.n_head, self.n_kv_head, table, None if doc is None else doc[2], inplace=True)
-        a = Fx.causal_attention(qkv, self.n_head, doc, n_kv_head=self.n_kv_head)
+        a = Fx.causal_attention(qkv, self.n_head, doc, n_kv_head=self.n_kv_head, window=self.window)
         x = Fx.linear_residual(a, self.attn_proj.weight, None, x)
         u = Fx.swiglu(self.c_fc(self.ln_2(x)))
         return Fx.linear_residual(u, self.mlp_proj.weight, None, x)
@@ -95,6 +97,8 @@ class Llama(GenerationMixin, nn.Module):
         super().__init__()
         if cfg.n_kv_head < 1 or cfg.n_head % cfg.n_kv_head:
             raise ValueError(f"n_head ({cfg.n_head}) must be a multiple of n_kv_head ({cfg.n_kv_head})")
+        if cfg.sliding_window < 0:
+            raise ValueError(f"sliding_window must be >= 1 (0 = none), got {cfg.sliding_window}")
         if cfg.n_embd != cfg.n_head * HEAD_DIM:
             raise ValueError(f"n_embd ({cfg.n_embd}) must be n_head * {HEAD_DIM}")
         self.cfg = cfg
@@ -173,7 +177,8 @@ class Llama(GenerationMixin, nn.Module):
             kv = qkv.view(B, T, Hq + 2 * Hkv, -1)
             cache.buf[l, 0, :, :, :T] = kv[:, :, Hq:Hq + Hkv].transpose(1, 2)
             cache.buf[l, 1, :, :, :T] = kv[:, :, Hq + Hkv:].transpose(1, 2)
-            x = Fx.linear_residual(Fx.causal_attention(qkv, Hq, n_kv_head=Hkv), blk.attn_proj.weight, None, x)
+            a = Fx.causal_attention(qkv, Hq, n_kv_head=Hkv, window=blk.window)
+            x = Fx.linear_residual(a, blk.attn_proj.weight, None, x)
             x = Fx.linear_residual(Fx.swiglu(blk.c_fc(blk.ln_2(x))), blk.mlp_proj.weight, None, x)
         last = x[torch.arange(B, device=x.device), lens.long() - 1]  # [B, D]
         return self._head(self.ln_f(last.unsqueeze(1)).squeeze(1))
@@ -188,7 +193,7 @@ class Llama(GenerationMixin, nn.Module):
         x = Fx.embedding(tok.view(B, 1), self.wte, None).view(B, -1)  # fp32 [B, D]
         for l, blk in enumerate(self.h):
             qkv = self._proj(blk.ln_1(x), blk.c_attn)
-            a = Fx.attn_decode_gqa(qkv, cache.buf[l, 0], cache.buf[l, 1], cache.len, Hq, Hkv, table)
+            a = Fx.attn_decode_gqa(qkv, cache.buf[l, 0], cache.buf[l, 1], cache.len, Hq, Hkv, table, window=blk.window or 0)
             x = self._proj(a, blk.attn_proj, residual=x)
             u = Fx.swiglu(self._proj(blk.ln_2(x), blk.c_fc))
             x = self._proj(u, blk.mlp_proj, residual=x)

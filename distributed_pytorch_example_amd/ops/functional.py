@@ -1070,7 +1070,7 @@ def check_doc_start(doc_start) -> None:
 
 class _AttnFn(Function):
     """The flash-attention kernels in any mode.  ``mode``: the keyword arguments of C.attn_fwd that select it (doc_start /
-    doc_end; dropout_p / rng / stream; causal / seq_len; n_kv_head), handed to C.attn_bwd unchanged -- under dropout rng
+    doc_end; dropout_p / rng / stream; causal / seq_len; n_kv_head; window), handed to C.attn_bwd unchanged -- under dropout rng
     is the forward's snapshot.  qkv: [B, T, 3, H, 64], or [B, T, H + 2 n_kv_head, 64]."""
 
     @staticmethod
@@ -1088,7 +1088,7 @@ class _AttnFn(Function):
         return ext().attn_bwd(qkv, out, dout.contiguous().to(torch.bfloat16), lse, H, scale, **mode), None, None, None
 
 
-def _gqa_attention(qkv, n_head: int, n_kv_head: int, doc_bounds):
+def _gqa_attention(qkv, n_head: int, n_kv_head: int, doc_bounds, window: int = 0):
     """causal_attention with n_kv_head: qkv [B, T, (Hq + 2 Hkv) * D]."""
     B, T, w = qkv.shape
     if n_kv_head < 1 or n_head % n_kv_head:
@@ -1097,13 +1097,13 @@ def _gqa_attention(qkv, n_head: int, n_kv_head: int, doc_bounds):
     scale = 1.0 / math.sqrt(D)
     ds, de = (doc_bounds[0], doc_bounds[1]) if doc_bounds is not None else (None, None)
     if qkv.is_cuda and attn_kernel_ok(T, D):
-        mode = dict(doc_start=ds, doc_end=de, n_kv_head=n_kv_head)
+        mode = dict(doc_start=ds, doc_end=de, n_kv_head=n_kv_head, window=window)
         return _AttnFn.apply(qkv.reshape(B, T, n_head + 2 * n_kv_head, D), n_head, scale, mode).reshape(B, T, n_head * D)
     # off the GPU and for other shapes: K / V expanded to one head per query head, then the explicit softmax
     q, k, v = qkv.reshape(B, T, n_head + 2 * n_kv_head, D).split([n_head, n_kv_head, n_kv_head], dim=2)
     g = n_head // n_kv_head
     qkv5 = torch.stack([q, k.repeat_interleave(g, dim=2), v.repeat_interleave(g, dim=2)], dim=2)
-    return _causal_attention_torch(qkv5, scale, ds).reshape(B, T, n_head * D)
+    return _causal_attention_torch(qkv5, scale, ds, window=window).reshape(B, T, n_head * D)
 
 
 def attn_kernel_ok(T: int, D: int) -> bool:
@@ -1111,11 +1111,12 @@ def attn_kernel_ok(T: int, D: int) -> bool:
     return D == 64 and T % 64 == 0
 
 
-def _causal_attention_torch(qkv5, scale: float, doc_start=None, dropout_p: float = 0.0):
+def _causal_attention_torch(qkv5, scale: float, doc_start=None, dropout_p: float = 0.0, window: int = 0):
     """Shapes outside the kernels' range (and every packed-document or dropout call off the GPU): explicit masked
     softmax(Q K^T) V in fp32 torch ops (autograd differentiates it), result in qkv's dtype like the kernel's.
     ``doc_start`` [B, T]: keys before the query's document are masked too.  ``dropout_p``: F.dropout on P (torch's
-    generator and the true p, not the kernels' Philox mask and 8-bit rate: the same distribution up to that)."""
+    generator and the true p, not the kernels' Philox mask and 8-bit rate: the same distribution up to that).
+    ``window`` W >= 1: keys before i - W + 1 are masked too."""
     q, k, v = qkv5.float().permute(2, 0, 3, 1, 4)  # each [B, H, T, D]
     T = q.shape[-2]
     s = (q @ k.transpose(-1, -2)) * scale
@@ -1123,6 +1124,8 @@ def _causal_attention_torch(qkv5, scale: float, doc_start=None, dropout_p: float
     if doc_start is not None:
         j = torch.arange(T, device=s.device)
         s = s.masked_fill((j[None, None, :] < doc_start.long()[:, :, None]).unsqueeze(1), float("-inf"))
+    if window:
+        s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=s.device).tril(-int(window)), float("-inf"))
     pr = torch.softmax(s, dim=-1)
     if dropout_p > 0.0:
         pr = F.dropout(pr, dropout_p, True)
@@ -1131,32 +1134,41 @@ def _causal_attention_torch(qkv5, scale: float, doc_start=None, dropout_p: float
 
 
 def causal_attention(qkv, n_head: int, doc_bounds=None, dropout_p: float = 0.0, rng=None, stream: int = 0,
-                     n_kv_head: Optional[int] = None):
+                     n_kv_head: Optional[int] = None, window: Optional[int] = None):
     """qkv: [B, T, 3*H*D] -> [B, T, H*D] causal softmax attention.  ``doc_bounds`` (the tuple doc_bounds()
     returns): attention stays inside each packed document.  ``dropout_p`` > 0 (training; the caller decides):
     dropout on the attention probabilities -- inside the flash kernels at the rate attn_dropout_rate(dropout_p),
     with the mask drawn from ``rng`` (a DropoutState snapshot, default: a fresh one, after which the state is
     advanced) and ``stream``; off the GPU or for other shapes an explicit softmax with F.dropout on P.
     ``n_kv_head``: grouped-query attention -- qkv is [B, T, (H + 2 * n_kv_head) * D], the H query heads, then the key
-    heads, then the value heads, and query head h attends to K / V head h // (H // n_kv_head); no dropout."""
+    heads, then the value heads, and query head h attends to K / V head h // (H // n_kv_head); no dropout.
+    ``window`` = W >= 1: sliding-window attention -- query i sees the keys max(doc_start[i], i - W + 1) .. i (None or 0:
+    no window; W >= T is plain causal attention).  It goes with packed documents and with n_kv_head; no dropout."""
+    window = 0 if window is None else int(window)
+    if window < 0:
+        raise ValueError(f"causal_attention: window must be >= 1 (None or 0 = no window), got {window}")
+    if window and dropout_p != 0.0:
+        raise ValueError("causal_attention: window has no attention dropout")
     if n_kv_head is not None:
         if dropout_p != 0.0:
             raise ValueError("causal_attention: n_kv_head has no attention dropout")
-        return _gqa_attention(qkv, n_head, n_kv_head, doc_bounds)
+        return _gqa_attention(qkv, n_head, n_kv_head, doc_bounds, window)
     B, T, three_hd = qkv.shape
     D = three_hd // (3 * n_head)
     scale = 1.0 / math.sqrt(D)
     if dropout_p != 0.0 and not 0.0 < dropout_p < 1.0:
         raise ValueError(f"dropout_p must be in [0, 1), got {dropout_p}")
     ds, de = (doc_bounds[0], doc_bounds[1]) if doc_bounds is not None else (None, None)
-    if not qkv.is_cuda and ds is None and dropout_p == 0.0:  # the plain causal call off the GPU, whatever its shape
+    if not qkv.is_cuda and ds is None and dropout_p == 0.0 and not window:  # the plain causal call off the GPU, whatever its shape
         q, k, v = qkv.float().view(B, T, 3, n_head, D).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return o.transpose(1, 2).reshape(B, T, n_head * D)
     qkv5 = qkv.reshape(B, T, 3, n_head, D)
     if not qkv.is_cuda or not attn_kernel_ok(T, D):
-        return _causal_attention_torch(qkv5, scale, ds, dropout_p).reshape(B, T, n_head * D)
+        return _causal_attention_torch(qkv5, scale, ds, dropout_p, window).reshape(B, T, n_head * D)
     mode = dict(doc_start=ds, doc_end=de)
+    if window:
+        mode.update(window=window)
     if dropout_p != 0.0:  # dropout on P inside the kernels; rng is the forward's snapshot, kept for backward
         if rng is None:
             st = dropout_state(qkv.device)
@@ -1421,13 +1433,14 @@ def attn_decode(qkv_step, kc, vc, lens, n_head: int, scale: Optional[float] = No
 
 
 def attn_decode_gqa(qkv_step, kc, vc, lens, n_head: int, n_kv_head: int, table, scale: Optional[float] = None,
-                    splits: int = 0):
+                    splits: int = 0, window: int = 0):
     """``attn_decode`` for grouped-query attention with the step's rotary embedding fused in.  qkv_step
     [B, (n_head + 2 n_kv_head) * D] is the new token's c_attn output, unrotated (query heads, key heads, value
     heads); kc / vc [B, n_kv_head, Tmax, D], kc holding rotated keys; ``table`` rope_table's (cos, sin).  With
     n = lens[b] clamped into [0, Tmax - 1]: the queries and the step's key are rotated by table row n (clamped into the
     table), row b attends keys 0 .. n of its KV head, and key n -- the rotated K, the V as it is -- is stored into the
-    cache.  Returns [B, n_head * D].  GPU: the HIP kernel (D = 64, at most 16 query heads per KV head; anything else
+    cache.  ``window`` = W >= 1: row b attends keys max(0, n - W + 1) .. n only (0 = no window; the cache keeps its Tmax
+    rows).  Returns [B, n_head * D].  GPU: the HIP kernel (D = 64, at most 16 query heads per KV head; anything else
     raises); elsewhere the same definition in torch ops on the cache's dtype."""
     B = qkv_step.shape[0]
     W = n_head + 2 * n_kv_head
@@ -1438,11 +1451,14 @@ def attn_decode_gqa(qkv_step, kc, vc, lens, n_head: int, n_kv_head: int, table, 
         raise ValueError(f"attn_decode_gqa: qkv_step and the [P, {table[0].shape[-1]}] table do not fit {W} heads")
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    window = int(window or 0)
+    if window < 0:
+        raise ValueError(f"attn_decode_gqa: window must be >= 1 (0 = no window), got {window}")
     if qkv_step.is_cuda:
         if D != 64 or G > 16:
             raise ValueError(f"attn_decode_gqa: the kernel takes head dim 64 and at most 16 query heads per KV head, got {D} and {G}")
         return ext().attn_decode_gqa(qkv_step.reshape(B, W, D), kc, vc, lens, table[0], table[1], n_kv_head, float(scale),
-                                     int(splits))
+                                     int(splits), window=window)
     Tmax = kc.shape[2]
     L = lens.long().clamp(0, Tmax - 1)
     x = _rope_torch(qkv_step.reshape(B, 1, W, D).to(kc.dtype), n_head + n_kv_head, table, L.view(B, 1)).view(B, W, D)
@@ -1450,7 +1466,8 @@ def attn_decode_gqa(qkv_step, kc, vc, lens, n_head: int, n_kv_head: int, table, 
     rows = torch.arange(B)
     kc[rows, :, L] = k
     vc[rows, :, L] = v
-    seen = (torch.arange(Tmax)[None, :] <= L[:, None])[:, None, None, :]  # [B, 1, 1, Tmax]
+    t = torch.arange(Tmax)[None, :]
+    seen = ((t <= L[:, None]) & (t > L[:, None] - (window or Tmax + 1)))[:, None, None, :]  # [B, 1, 1, Tmax]
     s = torch.einsum("bkgd,bktd->bkgt", q.float().view(B, n_kv_head, G, D), kc.float()) * scale
     p = torch.softmax(torch.where(seen, s, torch.full_like(s, float("-inf"))), dim=-1)
     vz = torch.where(seen.squeeze(2).unsqueeze(-1), vc.float(), torch.zeros((), dtype=torch.float32))

@@ -112,6 +112,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--doc-len-mean", type=float, default=None,
                    help="gpt2 and llama models: pack documents of this mean length (geometric) into every row; attention stays "
                         "inside a document, positions restart, targets across a boundary are ignored")
+    p.add_argument("--sliding-window", type=int, default=None,
+                   help="llama models: every layer's query attends the last W keys only (sliding-window attention; 0 = off)")
     p.add_argument("--max-steps", type=int, default=None, help="stop each epoch after this many steps")
     p.add_argument("--async-checkpoint", action="store_true")
     p.add_argument("--auto-resume", action="store_true", help="resume from <checkpoint-dir>/latest_model.pt if present")
@@ -281,6 +283,10 @@ def main(argv=None):
         parser.error("--doc-len-mean needs a gpt2 model or a llama model")
     if args.doc_len_mean is not None and not args.doc_len_mean >= 1:
         parser.error("--doc-len-mean must be >= 1")
+    if args.sliding_window is not None and args.model not in LLAMA_MODELS:
+        parser.error("--sliding-window needs a llama model")
+    if args.sliding_window is not None and args.sliding_window < 0:
+        parser.error("--sliding-window must be >= 1 (0 = off)")
     if args.trust_coefficient is not None and args.optimizer not in ("lars", "lamb"):
         parser.error("--trust-coefficient needs --optimizer lars or lamb")
     for flag, v in (("--muon-momentum", args.muon_momentum), ("--muon-ns-steps", args.muon_ns_steps)):
@@ -338,6 +344,8 @@ def main(argv=None):
     reg_kw = {"label_smoothing": args.label_smoothing, "z_loss": args.z_loss}
     if args.model.startswith("gpt2"):
         reg_kw["dropout"] = args.dropout
+    if args.sliding_window:
+        reg_kw["sliding_window"] = args.sliding_window
     model_kw = reg_kw if lm else ({"image_size": args.image_size} if vit or convnext else {})
     model = get_model(args.model, **_dtype_kw(args), **model_kw).to(device)
     model = DDP(model, bucket_cap_mb=args.bucket_mb,
